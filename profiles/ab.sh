@@ -10,7 +10,7 @@ timeout -k 10 300 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 tail -1 "$OUT/pytest_gpu.log"
 for lib in "$@"; do
   n=$(basename "$lib" .so)
-  BSDC_LIB_PATH=$(realpath "$lib") timeout -k 10 300 python -u bench.py --cpu-sample 0 > "$OUT/bench_$n.log" 2>&1 \
+  BSDC_LIB_PATH=$(realpath "$lib") timeout -k 10 300 python -u bench.py --full --cpu-sample 0 > "$OUT/bench_$n.log" 2>&1 \
     || { echo "bench $n failed"; tail -20 "$OUT/bench_$n.log"; exit 1; }
   echo "$n $(tail -1 "$OUT/bench_$n.log" | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["roofline"]["kernel_ms"], d["roofline"]["frac"])')"
   BSDC_LIB_PATH=$(realpath "$lib") timeout -k 10 300 python -u profiles/ablate.py > "$OUT/ablate_$n.log" 2>&1 \

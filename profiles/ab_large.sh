@@ -14,7 +14,7 @@ done
 for c in ${CFGS:-C3 C4}; do
   for lib in "$@"; do
     n=$(basename "$lib" .so)
-    BSDC_LIB_PATH=$(realpath "$lib") timeout -k 10 300 python -u bench.py --config $c --cpu-sample 0 --steps 10 > "$OUT/bench_${c}_$n.log" 2>&1 \
+    BSDC_LIB_PATH=$(realpath "$lib") timeout -k 10 300 python -u bench.py --full --config $c --cpu-sample 0 --steps 10 > "$OUT/bench_${c}_$n.log" 2>&1 \
       || { echo "bench $c $n failed"; tail -20 "$OUT/bench_${c}_$n.log"; exit 1; }
     echo "$c $n $(tail -1 "$OUT/bench_${c}_$n.log" | python -c 'import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; print(d["value"], d["ms_per_step"], r["small_kernel_ms"], r["large_kernel_ms"])')"
   done

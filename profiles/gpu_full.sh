@@ -11,6 +11,6 @@ tail -1 "$OUT/pytest_gpu.log"
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || { tail -20 "$OUT/smoke.log"; exit 1; }
 tail -1 "$OUT/smoke.log"
 for c in C2 C3; do
-  timeout -k 10 300 python -u bench.py --config $c --cpu-sample 0 --cpu-sample-1core 0 > "$OUT/bench_$c.log" 2>&1 || { echo "bench $c failed"; tail -20 "$OUT/bench_$c.log"; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --config $c --cpu-sample 0 --cpu-sample-1core 0 > "$OUT/bench_$c.log" 2>&1 || { echo "bench $c failed"; tail -20 "$OUT/bench_$c.log"; exit 1; }
   echo "$c $(tail -1 "$OUT/bench_$c.log" | cut -c1-300)"
 done

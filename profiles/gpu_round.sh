@@ -15,7 +15,7 @@ echo "[$(date +%T)] smoke"
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || { tail -20 "$OUT/smoke.log"; exit 1; }
 tail -1 "$OUT/smoke.log"
 echo "[$(date +%T)] bench (driver default)"
-timeout -k 10 400 python -u bench.py > "$OUT/bench_default.log" 2>&1 || { tail -20 "$OUT/bench_default.log"; exit 1; }
+timeout -k 10 400 python -u bench.py --full > "$OUT/bench_default.log" 2>&1 || { tail -20 "$OUT/bench_default.log"; exit 1; }
 tail -1 "$OUT/bench_default.log" | cut -c1-400
 echo "[$(date +%T)] ablate"
 timeout -k 10 200 python -u profiles/ablate.py --config C3 --kernel large > "$OUT/ablate_C3.log" 2>&1 || { tail -20 "$OUT/ablate_C3.log"; exit 1; }

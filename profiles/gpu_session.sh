@@ -14,10 +14,10 @@ timeout -k 10 400 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout
   || { echo "gpu tests failed"; tail -40 "$OUT/pytest_gpu.log"; exit 1; }
 tail -3 "$OUT/pytest_gpu.log"
 step bench
-timeout -k 10 400 python -u bench.py > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -20 "$OUT/bench.log"; exit 1; }
+timeout -k 10 400 python -u bench.py --full > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -20 "$OUT/bench.log"; exit 1; }
 tail -1 "$OUT/bench.log"
 step rocprof-stats
-(cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench -- python3 "$R/bench.py" --steps 10 --cpu-sample 0 > "$OUT/prof.log" 2>&1) \
+(cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench -- python3 "$R/bench.py" --full --steps 10 --cpu-sample 0 > "$OUT/prof.log" 2>&1) \
   || { echo "rocprof failed"; tail -20 "$OUT/prof.log"; exit 1; }
 find "$OUT/prof" -type f | head -20; find "$OUT/prof" -name '*kernel_stats.csv' -exec head -6 {} \;
 step ablate

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 for c in ${CONFIGS:-C2 C3}; do
   echo "[$(date +%T)] stats $c"
   (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$c" -o bench -- \
-      python3 "$R/bench.py" --config $c --steps 20 --cpu-sample 0 --cpu-sample-1core 0 --no-tags-leg > "$OUT/prof_$c.log" 2>&1) \
+      python3 "$R/bench.py" --full --config $c --steps 20 --cpu-sample 0 --cpu-sample-1core 0 --no-tags-leg > "$OUT/prof_$c.log" 2>&1) \
     || { echo "rocprof $c failed"; tail -20 "$OUT/prof_$c.log"; exit 1; }
   tail -1 "$OUT/prof_$c.log" | cut -c1-200
   find "$OUT/prof_$c" -name '*kernel_stats.csv' -exec cat {} \;

@@ -18,8 +18,8 @@ def test_bench_two_ranks_on_one_gpu():
     fams, steps = 50_000, 3
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "profiles", "rehearse_bench_ranks.py"), "--ranks", "2", "--",
-                        "--families", str(fams), "--steps", str(steps), "--warmup", "1", "--cpu-sample", "0",
-                        "--no-tags-leg"], capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
+                        "--full", "--families", str(fams), "--steps", str(steps), "--warmup", "1",
+                        "--cpu-sample", "0", "--no-tags-leg"], capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-3000:]  # rank 0 alone prints
