@@ -25,6 +25,7 @@ from . import _lib
 from . import records as R
 
 LINK_MATE_NONE = 0xFFFF
+MAX_FAMILY_RECORDS = 0xFFFE  # BSDC_MAX_FAMILY_RECORDS: every in-family index stays below LINK_MATE_NONE
 LINK_AB = 1 << 16
 LINK_BA = 1 << 17
 LINK_COMPLEX = 1 << 18
@@ -765,10 +766,12 @@ def materialize_py(plan: FamilyPlan, f0: int, f1: int, small_cap: int = SMALL_AR
     t2_rank = plan.t2_rank[r0:r1]
     nr = int(order.shape[0])
     nf = int(fam_sizes.shape[0])
+    if nf and int(fam_sizes.max()) > MAX_FAMILY_RECORDS:
+        raise ValueError("family of more than 65534 records (BSDC_MAX_FAMILY_RECORDS: 16-bit mate index)")
     fam_off = np.zeros(nf + 1, np.int64)
     fam_off[1:] = np.cumsum(fam_sizes)
     fam_of = np.repeat(np.arange(nf, dtype=np.int64), fam_sizes)
-    local = np.arange(nr, dtype=np.int64) - fam_off[fam_of]
+    local =np.arange(nr, dtype=np.int64) - fam_off[fam_of]
     # extension partners as family-local indices (a partner outside the family -- plan.fam_split --
     # makes the fused launch invalid; the caller then runs the tools and the vote apart)
     has_p = (ext_right | ext_left)[order]

@@ -471,6 +471,12 @@ int32_t bsdc_materialize_prepare(const bsdc_host_records *R, const bsdc_host_ref
     b->rec_off.resize(nr);
     b->img.resize(nf);
     b->fam_base.assign(nf + 1, 0);
+    // the link word's in-family mate index is 16 bits with 0xFFFF = none (BSDC_LINK_MATE_MASK)
+    for (int64_t f = 0; f < nf; f++)
+        if (pv->fam_off[f0 + f + 1] - pv->fam_off[f0 + f] > BSDC_MAX_FAMILY_RECORDS) {
+            delete b;
+            return fail(BSDC_EINVAL, "family of more than 65534 records (BSDC_MAX_FAMILY_RECORDS: 16-bit mate index)");
+        }
     int64_t nb = 0, ncig = 0;
     int32_t ml = 0;
 #pragma omp parallel for schedule(static) reduction(+ : nb, ncig) reduction(max : ml)

@@ -3104,15 +3104,33 @@ int32_t bsdc_host_unregister(int32_t device, void *ptr) {
     return 0;
 }
 
-static bool params_ok(const bsdc_params *p) {
-    return p->min_reads == 0 && p->min_input_base_quality >= 0 && p->min_consensus_base_quality >= 0 &&
-           p->min_consensus_base_quality <= 94;
+// The supported parameter domain (include/bsdc.h bsdc_params), nullptr when `p` is inside it.
+// The agreement case reads dthr[Q + 1] (Tables::dthr, 48 entries) with Q the column's quality,
+// which reaches the largest k whose threshold is not negative, floor(pre + 0.001): the pre-UMI
+// rate must keep that at 46 or less.
+static const char *params_error(const bsdc_params *p) {
+    if (p->min_reads != 0) return "bad params: min_reads: only 0 is supported";
+    if (p->min_input_base_quality != 0) return "bad params: min_input_base_quality: only 0 is supported";
+    if (p->min_consensus_base_quality < 0 || p->min_consensus_base_quality > 94)
+        return "bad params: min_consensus_base_quality outside 0..94";
+    const double pre = p->error_rate_pre_umi, post = p->error_rate_post_umi;
+    // (NaN fails every comparison; at pre <= 10 log10(4/3) the thresholds' 1 - 4/3 e_pre is not positive)
+    if (!(pre >= 1.25) || !(post > 0.0) || !(post <= 1000.0))
+        return "bad params: error rates are phred values: pre-UMI at least 1.25, post-UMI in (0, 1000]";
+    // thr[47] as make_tables computes it: negative <=> no column reaches Q47
+    const double e_pre = pow(10.0, -pre / 10.0);
+    const double pk = pow(10.0, -(47.0 - 0.001) / 10.0);
+    if (!((pk - e_pre) / (1.0 - (4.0 / 3.0) * e_pre) < 0.0))
+        return "bad params: error_rate_pre_umi must be below 46.999 (consensus qualities above 46 are not tabulated)";
+    return nullptr;
 }
+// bsdc_ctx_create's refusal of its params: there is no context to hold it (bsdc_last_error(NULL))
+static thread_local const char *g_create_err = "null context";
 
 int32_t bsdc_ctx_set_params(bsdc_ctx *c, const bsdc_params *params) {
     if (!c || !params) return BSDC_EINVAL;
-    if (!params_ok(params)) {
-        c->err = "bad params";
+    if (const char *why = params_error(params)) {
+        c->err = why;
         return BSDC_EINVAL;
     }
     if (params->error_rate_pre_umi != c->params.error_rate_pre_umi ||
@@ -3167,7 +3185,10 @@ void bsdc_phred_buckets(double pre, double post, uint8_t *sq144) {
 int32_t bsdc_ctx_create(int32_t device, const bsdc_params *params, bsdc_ctx **out) {
     if (!out || !params) return BSDC_EINVAL;
     *out = nullptr;
-    if (!params_ok(params)) return BSDC_EINVAL;
+    if (const char *why = params_error(params)) {
+        g_create_err = why;
+        return BSDC_EINVAL;
+    }
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return BSDC_EDEVICE;
     bsdc_ctx *c = new bsdc_ctx();
@@ -3207,7 +3228,7 @@ void bsdc_ctx_destroy(bsdc_ctx *c) {
     delete c;
 }
 
-const char *bsdc_last_error(const bsdc_ctx *c) { return c ? c->err.c_str() : "null context"; }
+const char *bsdc_last_error(const bsdc_ctx *c) { return c ? c->err.c_str() : g_create_err; }
 
 int32_t bsdc_get_tables(const bsdc_ctx *c, int64_t *lr256, float *thr94) {
     if (!c) return BSDC_EINVAL;

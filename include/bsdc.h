@@ -35,11 +35,25 @@ extern "C" {
 #define BSDC_ENOMEM (-12)
 #define BSDC_EDEVICE (-5)
 
-/* fgbio CallDuplexConsensusReads flags as the pipeline passes them (main.snake.py:163) */
+/* fgbio CallDuplexConsensusReads flags as the pipeline passes them (main.snake.py:163).
+ *
+ * Supported domain -- bsdc_ctx_create and bsdc_ctx_set_params return BSDC_EINVAL outside it, with
+ * the reason in bsdc_last_error (of the context; bsdc_last_error(NULL) after a failed create):
+ *   error_rate_pre_umi   1.25 <= pre < 46.999.  A consensus quality reaches floor(pre + 0.001), and
+ *                        the vote's agreement-case table (dthr, 48 entries, read at Q + 1) covers
+ *                        qualities up to 46.  The pipeline passes 45.
+ *   error_rate_post_umi  0 < post <= 1000.
+ *   min_input_base_quality  only 0: no kernel masks input bases, so another value is refused
+ *                        instead of being ignored.
+ *   min_reads            only 0.
+ *   min_consensus_base_quality  0..94 (94: every single-strand column is (N, 2)).
+ * Quality bytes are unsigned phred values 0..255 everywhere (overlap consensus, vote: lr has 256
+ * entries): a byte above 93, BAM's "missing quality" 0xFF included, is that phred and not a
+ * marker; only results are capped at 93. */
 typedef struct {
     double error_rate_pre_umi;                /* --error-rate-pre-umi=45 */
     double error_rate_post_umi;               /* --error-rate-post-umi=30 */
-    int32_t min_input_base_quality;           /* --min-input-base-quality=0 */
+    int32_t min_input_base_quality;           /* --min-input-base-quality=0 (only 0 is supported) */
     int32_t consensus_call_overlapping_bases; /* --consensus-call-overlapping-bases=true */
     int32_t min_reads;                        /* --min-reads=0 (only 0 is supported) */
     int32_t min_consensus_base_quality;       /* single-strand calls with Q below it -> (N, 2), 0..94:
@@ -51,6 +65,8 @@ typedef struct {
 
 /* Per-record `link` word (host-built) */
 #define BSDC_LINK_MATE_MASK 0xFFFFu   /* template mate (R2 of this R1) index within family; 0xFFFF = none */
+#define BSDC_MAX_FAMILY_RECORDS 65534 /* so every in-family index stays below 0xFFFF; the host planner
+                                         (bsdc_materialize_prepare, batch.materialize_py) refuses larger families */
 #define BSDC_LINK_AB (1u << 16)       /* MI ends in /A */
 #define BSDC_LINK_BA (1u << 17)       /* MI ends in /B */
 #define BSDC_LINK_COMPLEX (1u << 18)  /* cigar is not a single M-like run: read cig_* */
@@ -204,7 +220,9 @@ void bsdc_model_tables(double error_rate_pre_umi, double error_rate_post_umi, in
 /* The near-tie tables: fgbio's per-read log-space terms in double precision,
    ln P(correct) and ln P(error) / 3 per phred, which a near-tie column sums in fgbio's read order. */
 void bsdc_model_tables_fp64(double error_rate_pre_umi, double error_rate_post_umi, double *lnc256, double *lne3_256);
-/* The vote's agreement-case tables: Q(D) = qlo[D >> 16] + (D >= dthr[qlo[D >> 16] + 1]). */
+/* The vote's agreement-case tables: Q(D) = qlo[D >> 16] + (D >= dthr[qlo[D >> 16] + 1]).
+   The table helpers here are unchecked: they tabulate any rates, also ones bsdc_ctx_create refuses
+   (for which dthr's 48 entries do not cover every reachable Q). */
 void bsdc_agree_tables(double error_rate_pre_umi, double error_rate_post_umi, uint8_t *qlo2048, int32_t *dthr48);
 /* The general case's phred buckets: Q(S) = the largest k >= sq[j] with S <= thresh[k], j = the
    bucket of S ((float bits >> 21) - ((127 - 32) << 2), clamped to [0, 135]). */

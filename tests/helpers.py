@@ -108,6 +108,69 @@ def near_tie_votes(raw, n_pos=6, seed=3, qlo=80, qhi=93, p_n=0.1, n_alleles=2):
     return dataclasses.replace(raw, seq=seq, qual=qual)
 
 
+def gpu_vs_fp64(engine, raw, ref, run_tools, what, molecular=False, pre=45.0, post=30.0, min_cbq=None,
+                overlap=True, dump=False):
+    """One GPU run against both references: oracle/ bit for bit (consensus, single-strand reads,
+    tag statistics) and the fp64 restatement of fgbio (tests/fgbio_vote.py) within the fp64 bar
+    (test_fgbio_vote.assert_fp64_bar), single-strand and duplex.  The engine runs with the given
+    flags for this call only; min_cbq defaults to the caller's own (0 molecular, 2 duplex).
+    dump (step 5 with the tools): also fetch the tool-2 records.
+    -> (Consensus, compare_ss counts, tool-2 records or None, OracleResult)."""
+    import fgbio_vote as fv
+    from bsseqconsensusreads_amd import pipeline
+    from oracle import oracle
+    from test_fgbio_vote import assert_fp64_bar
+    from test_gpu_parity import assert_consensus_equal, assert_ss_equal
+    engine.load_reference(ref)
+    if min_cbq is None:
+        min_cbq = 0 if molecular else 2  # main.snake.py:54 vs the duplex caller's single-strand caller
+    t2 = None
+    with engine.flags(error_rate_pre_umi=pre, error_rate_post_umi=post, consensus_call_overlapping_bases=overlap,
+                      min_consensus_base_quality=min_cbq):
+        if molecular:
+            cons, raw = pipeline.run_molecular(engine, raw, tags=True, min_consensus_base_quality=min_cbq)
+            r = oracle.run(raw, ref, pre=pre, post=post, overlap=overlap, keep_sources=True, run_tools=False,
+                           family_order="mi-group", min_consensus_base_quality=min_cbq)
+        else:
+            if run_tools:
+                cons, t2 = pipeline.run_step5(engine, raw, dump=dump, tags=True)
+            else:
+                cons = pipeline.run_duplex(engine, raw, tags=True)
+            r = oracle.run(raw, ref, pre=pre, post=post, overlap=overlap, keep_sources=True, run_tools=run_tools,
+                           min_consensus_base_quality=min_cbq)
+    assert_consensus_equal(cons, r, what)      # GPU == fixed-point restatement, bit for bit
+    assert_ss_equal(cons, r, what)
+    src = r.sources
+    stride = cons.ss["base"].shape[2]
+    ss = fv.ss_vote(src["count"], src["len"], src["base"], src["qual"], stride, pre=pre, post=post, min_cbq=min_cbq)
+    em = np.nonzero((cons.status & 1) != 0)[0]  # (the kernels' single-strand reads: emitted families)
+    c = fv.compare_ss({"len": cons.ss["len"][em], "base": cons.ss["base"][em], "qual": cons.ss["qual"][em]},
+                      {k: v[em] for k, v in ss.items()})
+    assert_fp64_bar(c, what)
+    # duplex consensus vs fgbio fp64 duplex of the fp64 single-strand reads
+    st, ln, b, q = fv.duplex(ss)
+    assert np.array_equal(st, (cons.status & 1).astype(np.int32)) and np.array_equal(ln, cons.length)
+    w = min(b.shape[2], cons.seq.shape[2])
+    live = np.arange(w)[None, None, :] < ln[:, :, None]
+    db = live & (cons.seq[:, :, :w] != b[:, :, :w])
+    dq = np.abs(cons.qual[:, :, :w].astype(np.int64) - q[:, :, :w].astype(np.int64))
+    print(what, "duplex columns %d, base diffs %d, qual +-1 %d, qual >1 %d" % (
+        int(live.sum()), int(db.sum()), int((live & (dq == 1)).sum()), int((live & (dq > 1)).sum())))
+    # a duplex column can differ only where one of its single-strand inputs does (a +-1 qual); with
+    # none of those (the usual case), the duplex reads are identical
+    same = np.ones(b.shape, bool)
+    for e, (sa, sb) in enumerate(((0, 3), (1, 2))):
+        for st_ in (sa, sb):
+            same[:, e, :w] &= (cons.ss["base"][:, st_, :w] == ss["base"][:, st_, :w]) & \
+                              (cons.ss["qual"][:, st_, :w] == ss["qual"][:, st_, :w])
+    same[(cons.status & 1) == 0] = True  # (no duplex read there: ln is 0)
+    assert not (db & same[:, :, :w]).any(), what + ": duplex base differs from fgbio fp64"
+    assert not (live & (dq > 0) & same[:, :, :w]).any(), what + ": duplex qual differs from fgbio fp64"
+    if c["qual_pm1"] == 0 and c["n_boundary"] == 0:
+        assert int(db.sum()) == 0 and int((live & (dq > 0)).sum()) == 0
+    return cons, c, t2, r
+
+
 def assert_bam_matches_oracle(out_bam, in_bam, fasta, what=""):
     """The step-5 output BAM, record by record (R1, R2 per emitted family, TemplateCoordinate
     order): name suffix, SEQ and QUAL against oracle/ on the whole input file."""

@@ -6,6 +6,7 @@ import os
 import numpy as np
 
 from bsseqconsensusreads_amd import _lib, batch
+from edge_inputs import RATES_ACCEPTED, RATES_REFUSED
 from oracle import oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -72,14 +73,60 @@ def test_arena_formulas_match_library():
 
 def test_agreement_tables_exhaustive():
     """The kernel's agreement-case shortcut (integer thresholds on the likelihood sum) gives the
-    same phred as the full float arithmetic of oracle/ for EVERY sum up to past saturation."""
+    same phred as the full float arithmetic of oracle/ for EVERY sum up to past saturation, at
+    every rate pair the library accepts -- with dthr as long as Tables::dthr is (48 entries): the
+    rule reads dthr[qlo + 1], so qlo must stay below 47."""
     lib = _lib.load()
-    for pre, post in ((45.0, 30.0), (40.0, 20.0)):
+    for pre, post in RATES_ACCEPTED:
         qlo = np.zeros(2048, np.uint8)
         dthr = np.zeros(48, np.int32)
         lib.bsdc_agree_tables(pre, post, qlo.ctypes.data, dthr.ctypes.data)
+        assert int(qlo.max()) + 1 < dthr.shape[0], (pre, post, int(qlo.max()))
         _, thr = oracle.tables(pre, post)
-        assert oracle.check_agree_tables(qlo, dthr, thr, (1 << 27) + 1000) == -1
+        assert oracle.check_agree_tables(qlo, dthr, thr, (1 << 27) + 1000) == -1, (pre, post)
+
+
+def _create(lib, *params):
+    """bsdc_ctx_create with these params -> (rc, message); a context that came up is destroyed."""
+    import ctypes as C
+    h = C.c_void_p()
+    p = _lib.Params(*params)
+    rc = lib.bsdc_ctx_create(0, C.byref(p), C.byref(h))
+    msg = lib.bsdc_last_error(None).decode()
+    if rc == 0:
+        lib.bsdc_ctx_destroy(h)
+    return rc, msg
+
+
+def test_params_outside_the_domain_are_refused():
+    """include/bsdc.h bsdc_params: a pre-UMI rate whose consensus qualities pass 46 would index
+    past Tables::dthr (the refused pairs' qlo shows it), min_input_base_quality is read by no
+    kernel, min_reads likewise: bsdc_ctx_create refuses each with a message that names the field,
+    before it touches a device.  Accepted params get past the check (no device here: EDEVICE)."""
+    lib = _lib.load()
+    EINVAL = -22
+    for pre, post in RATES_REFUSED:
+        qlo = np.zeros(2048, np.uint8)
+        dthr = np.zeros(48, np.int32)
+        lib.bsdc_agree_tables(pre, post, qlo.ctypes.data, dthr.ctypes.data)  # (the helpers are unchecked)
+        assert int(qlo.max()) + 1 >= dthr.shape[0]
+        rc, msg = _create(lib, pre, post, 0, 1, 0, 2)
+        assert rc == EINVAL and "error_rate_pre_umi" in msg, (pre, post, rc, msg)
+    for pre, post in ((46.999, 30.0), (47.0, 30.0), (float("nan"), 30.0), (0.0, 30.0), (45.0, 0.0), (45.0, -1.0),
+                      (45.0, float("inf"))):
+        rc, msg = _create(lib, pre, post, 0, 1, 0, 2)
+        assert rc == EINVAL and "error" in msg, (pre, post, rc, msg)
+    for mibq in (1, 10, -1):
+        rc, msg = _create(lib, 45.0, 30.0, mibq, 1, 0, 2)
+        assert rc == EINVAL and "min_input_base_quality: only 0 is supported" in msg, (mibq, rc, msg)
+    rc, msg = _create(lib, 45.0, 30.0, 0, 1, 1, 2)
+    assert rc == EINVAL and "min_reads" in msg
+    for mcbq in (-1, 95):
+        rc, msg = _create(lib, 45.0, 30.0, 0, 1, 0, mcbq)
+        assert rc == EINVAL and "min_consensus_base_quality" in msg
+    for pre, post in RATES_ACCEPTED + ((46.99, 30.0), (1.25, 93.0)):
+        for mcbq in (0, 94):
+            assert _create(lib, pre, post, 0, 0, 0, mcbq)[0] != EINVAL, (pre, post)
 
 
 def test_phred_buckets_match_threshold_scan():

@@ -10,60 +10,16 @@ path (fp64_pick) reproduces it.  Counts are printed (run with -s) and asserted.
 import numpy as np
 import pytest
 
-import fgbio_vote as fv
 from bsseqconsensusreads_amd import batch, pipeline, synth
-from helpers import near_tie_votes
-from oracle import oracle
-from test_fgbio_vote import CASES, assert_fp64_bar, low_quality_votes
-from test_gpu_parity import assert_consensus_equal, assert_ss_equal
+from helpers import gpu_vs_fp64, near_tie_votes
+from test_fgbio_vote import CASES, low_quality_votes
 
 pytestmark = pytest.mark.gpu
 
 
 def _gpu_vs_fp64(engine, raw, ref, run_tools, what, molecular=False):
-    engine.load_reference(ref)
-    min_cbq = 0 if molecular else 2  # main.snake.py:54 vs the duplex caller's single-strand caller
-    if molecular:
-        cons, raw = pipeline.run_molecular(engine, raw, tags=True)
-        r = oracle.run(raw, ref, keep_sources=True, run_tools=False, family_order="mi-group",
-                       min_consensus_base_quality=0)
-    else:
-        if run_tools:
-            cons, _ = pipeline.run_step5(engine, raw, tags=True)
-        else:
-            cons = pipeline.run_duplex(engine, raw, tags=True)
-        r = oracle.run(raw, ref, keep_sources=True, run_tools=run_tools)
-    assert_consensus_equal(cons, r, what)      # GPU == fixed-point restatement, bit for bit
-    assert_ss_equal(cons, r, what)
-    src = r.sources
-    stride = cons.ss["base"].shape[2]
-    ss = fv.ss_vote(src["count"], src["len"], src["base"], src["qual"], stride, min_cbq=min_cbq)
-    em = np.nonzero((cons.status & 1) != 0)[0]  # (the kernels' single-strand reads: emitted families)
-    c = fv.compare_ss({"len": cons.ss["len"][em], "base": cons.ss["base"][em], "qual": cons.ss["qual"][em]},
-                      {k: v[em] for k, v in ss.items()})
-    assert_fp64_bar(c, what)
-    # duplex consensus vs fgbio fp64 duplex of the fp64 single-strand reads
-    st, ln, b, q = fv.duplex(ss)
-    assert np.array_equal(st, (cons.status & 1).astype(np.int32)) and np.array_equal(ln, cons.length)
-    w = min(b.shape[2], cons.seq.shape[2])
-    live = np.arange(w)[None, None, :] < ln[:, :, None]
-    db = live & (cons.seq[:, :, :w] != b[:, :, :w])
-    dq = np.abs(cons.qual[:, :, :w].astype(np.int64) - q[:, :, :w].astype(np.int64))
-    print(what, "duplex columns %d, base diffs %d, qual +-1 %d, qual >1 %d" % (
-        int(live.sum()), int(db.sum()), int((live & (dq == 1)).sum()), int((live & (dq > 1)).sum())))
-    # a duplex column can differ only where one of its single-strand inputs does (a +-1 qual); with
-    # none of those (the usual case), the duplex reads are identical
-    same = np.ones(b.shape, bool)
-    for e, (sa, sb) in enumerate(((0, 3), (1, 2))):
-        for st_ in (sa, sb):
-            same[:, e, :w] &= (cons.ss["base"][:, st_, :w] == ss["base"][:, st_, :w]) & \
-                              (cons.ss["qual"][:, st_, :w] == ss["qual"][:, st_, :w])
-    same[(cons.status & 1) == 0] = True  # (no duplex read there: ln is 0)
-    assert not (db & same[:, :, :w]).any(), what + ": duplex base differs from fgbio fp64"
-    assert not (live & (dq > 0) & same[:, :, :w]).any(), what + ": duplex qual differs from fgbio fp64"
-    if c["qual_pm1"] == 0 and c["n_boundary"] == 0:
-        assert int(db.sum()) == 0 and int((live & (dq > 0)).sum()) == 0
-    return cons
+    """helpers.gpu_vs_fp64 (shared with tests/test_gpu_edges.py) at the default flags."""
+    return gpu_vs_fp64(engine, raw, ref, run_tools, what, molecular=molecular)[0]
 
 
 @pytest.mark.parametrize("cfg,n,qlo", CASES)

@@ -86,6 +86,53 @@ def test_split_partner_and_missing_mi():
         hostplan.plan_families(raw, "full", s.ref)
 
 
+def _one_family(n_templates):
+    """One MI family of n_templates one-template pairs (99 / 147) of 1-base reads at one position."""
+    from bsseqconsensusreads_amd import records as R
+    n = 2 * n_templates
+    r1 = np.arange(n) % 2 == 0
+    z, one = np.zeros(n, np.int32), np.ones(n, np.int32)
+    raw = R.RawRecords(
+        flag=np.where(r1, 99, 147).astype(np.uint16), tid=z, pos=np.full(n, 50, np.int32), mapq=np.full(n, 60, np.uint8),
+        l_seq=one, seq_off=np.arange(n, dtype=np.int64), seq=np.full(n, 1, np.uint8), qual=np.full(n, 30, np.uint8),
+        cig_off=np.arange(n, dtype=np.int64), n_cig=one, cigar=np.full(n, (1 << 4) | R.OP_M, np.uint32), next_tid=z,
+        next_pos=np.full(n, 50, np.int32), tlen=np.where(r1, 1, -1).astype(np.int32),
+        name_id=(np.arange(n) // 2).astype(np.int32), names=synth._LazyNames("t"), mi_id=z, mi_strand=np.zeros(n, np.int8),
+        mi_names=synth._LazyNames(""), mc_off=np.arange(n, dtype=np.int64), mc_n=one,
+        mc_cigar=np.full(n, (1 << 4) | R.OP_M, np.uint32))
+    return raw, R.Reference.from_codes(["chrL"], [np.full(200, 1, np.uint8)])
+
+
+@pytest.mark.parametrize("native", [True, False])
+def test_family_size_limit(native):
+    """The link word's in-family mate index is 16 bits with 0xFFFF = none (BSDC_LINK_MATE_MASK), so
+    a family holds at most BSDC_MAX_FAMILY_RECORDS = 65534 records: the largest one materializes
+    with every R1's mate index right (the last one's included), one template more -- index 0xFFFF
+    would read as "no mate" -- and 65,536 templates -- indices past 16 bits would overwrite the
+    strand bits -- are refused by name, in the C++ planner and in the numpy statement.  No kernel
+    runs."""
+    plan_f = hostplan.plan_families if native else batch.plan_families_py
+    mat = (lambda p: hostplan.materialize(p, 0, p.n_fam, 0)) if native else (lambda p: batch.materialize_py(p, 0, p.n_fam, 0))
+    assert batch.MAX_FAMILY_RECORDS == 65534
+    raw, ref = _one_family(batch.MAX_FAMILY_RECORDS // 2)
+    fb = mat(plan_f(raw, "full", ref))
+    assert fb.n_fam == 1 and fb.n_rec == batch.MAX_FAMILY_RECORDS
+    local = np.empty(fb.n_rec, np.int64)
+    local[fb.src] = np.arange(fb.n_rec)              # family-local index of each input record
+    is_r1 = (fb.rec_lenflag >> 16) == 99
+    mate = (fb.rec_link & batch.LINK_MATE_NONE).astype(np.int64)
+    assert np.array_equal(mate[is_r1], local[fb.src[is_r1] + 1])  # R2 follows its R1 in the input
+    assert (mate[~is_r1] == batch.LINK_MATE_NONE).all()
+    last_r1 = int(np.nonzero(is_r1)[0][-1])
+    assert last_r1 >= fb.n_rec - 2 and mate[last_r1] == local[fb.src[last_r1] + 1] < batch.LINK_MATE_NONE
+    assert mate[is_r1].max() == batch.MAX_FAMILY_RECORDS - 1  # the largest index in use, below "none"
+    assert ((fb.rec_link & (batch.LINK_AB | batch.LINK_BA)) == batch.LINK_AB).all()
+    for n_templates in (batch.MAX_FAMILY_RECORDS // 2 + 1, 65536):
+        raw, ref = _one_family(n_templates)
+        with pytest.raises(ValueError, match="65534 records"):
+            mat(plan_f(raw, "full", ref))
+
+
 def test_empty_input():
     s = synth.generate("C0", 10, seed=1, device="cpu", genome_len=20_000)
     from bsseqconsensusreads_amd import records as R
