@@ -22,6 +22,16 @@
 //     (shared) words by atomicOr into the zeroed slot.
 // Bytes per block: 65280 in, ~9.3 KB out for the tagged step-5 output (ratio 7.0 against libdeflate
 // level 5's 7.26, profiles/deflate_levels.py).
+//
+// Tested paths (tests/test_gpu_bgzf_edges.py on the inputs of tests/bgzf_inputs.py, byte for byte
+// against the restatement): the length-limit retry of huffman_lengths for all three alphabets
+// (literal/length, distance, code-length -- none stays unreached), a copy at distance 32768 taken
+// and at 32769 cut in A2, chains cut at kChain, in-round candidates across the wave boundaries,
+// table collisions, the lazy rule at 31 | 32, the kNice stop at 63 | 64, matches clipped at the
+// segment end (255 is the longest: length 258 and hlit 286 cannot occur), blocks with one distance
+// code or none, partial blocks (n = 1 .. 65279, a 1-byte last block) through the C-ABI, and
+// k_bgzf_pack's prefix sum over more than 256 earlier blocks.  Not reached: a block that does not
+// fit (sizes = 0); no input is known to give one.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -49,12 +49,15 @@ static int dist_code(int d) {
     return c;
 }
 
-/* Huffman code lengths of n symbols (freq 0: length 0), longest <= limit.  Two queues over the
+/* Huffman code lengths of n symbols (freq 0: length 0), longest <= limit: the number of retries
+ * (*single: the one-used-symbol path ran).  Two queues over the
  * leaves sorted by (frequency, symbol); on equal weight the leaf queue goes first.  Too deep:
  * every nonzero frequency becomes (f >> 1) | 1 and the code is built again.  One used symbol gets
  * length 1. */
-void bgzf_huffman_lengths(const uint32_t *freq_in, int n, int limit, uint8_t *len) {
+static int huffman_lengths(const uint32_t *freq_in, int n, int limit, uint8_t *len, int *single) {
     uint32_t f[288];
+    int retries = 0;
+    if (single) *single = 0;
     for (int i = 0; i < n; i++) f[i] = freq_in[i];
     for (;;) {
         int leaf[288], nl = 0;
@@ -62,10 +65,11 @@ void bgzf_huffman_lengths(const uint32_t *freq_in, int n, int limit, uint8_t *le
             len[i] = 0;
             if (f[i]) leaf[nl++] = i;
         }
-        if (nl == 0) return;
+        if (nl == 0) return retries;
         if (nl == 1) {
             len[leaf[0]] = 1;
-            return;
+            if (single) *single = 1;
+            return retries;
         }
         for (int i = 1; i < nl; i++) {  // insertion sort by (freq, symbol)
             const int x = leaf[i];
@@ -105,10 +109,14 @@ void bgzf_huffman_lengths(const uint32_t *freq_in, int n, int limit, uint8_t *le
                 if (depth[i] > maxd) maxd = depth[i];
             }
         }
-        if (maxd <= limit) return;
+        if (maxd <= limit) return retries;
+        retries++;
         for (int i = 0; i < n; i++)
             if (f[i]) f[i] = (f[i] >> 1) | 1u;
     }
+}
+void bgzf_huffman_lengths(const uint32_t *freq_in, int n, int limit, uint8_t *len) {
+    huffman_lengths(freq_in, n, limit, len, NULL);
 }
 
 /* canonical codes (RFC 1951 3.2.2), bit-reversed for the LSB-first stream */
@@ -210,12 +218,18 @@ static uint32_t crc32_bytes(const uint8_t *p, int64_t n) {
 }
 
 /* the longest match at i (0 if none of length >= 1): distances 1, 2, 4, then down the chain,
- * until one is kNice long */
-static void best_match(const uint8_t *in, const int32_t *cand, int i, int s1, int *pl, int *pd) {
+ * until one is kNice long.  st (may be NULL: the lazy look-ahead, whose position is searched again
+ * when it becomes the token's) counts how the chain and the search ended. */
+static void best_match(const uint8_t *in, const int32_t *cand, int i, int s1, int *pl, int *pd, bgzf_ref_stats *st) {
     const int maxl = s1 - i < 258 ? s1 - i : 258;
     int cd[3 + kChain] = {1, 2, 4};
     int nc = 3;
-    for (int c = cand[i]; c >= 0 && nc < 3 + kChain && i - c <= kMaxDist; c = cand[c]) cd[nc++] = i - c;
+    int c = cand[i];
+    for (; c >= 0 && nc < 3 + kChain && i - c <= kMaxDist; c = cand[c]) cd[nc++] = i - c;
+    if (st && c >= 0) {
+        if (i - c > kMaxDist) st->chain_cut_maxdist++;
+        else st->chain_cut_kchain++;
+    }
     int bestl = 0, bestd = 0;
     for (int k = 0; k < nc; k++) {
         const int d = cd[k];
@@ -226,15 +240,20 @@ static void best_match(const uint8_t *in, const int32_t *cand, int i, int s1, in
             bestl = l;
             bestd = d;
         }
-        if (bestl >= kNice) break;
+        if (bestl >= kNice) {
+            if (st) st->nice_stops++;
+            break;
+        }
     }
     *pl = bestl;
     *pd = bestd;
 }
 
 /* One BGZF block of in[0, n) (1 <= n <= 65280) into out (65536 bytes): its size, or 0 when the
- * dynamic block does not fit (the caller then stores the block). */
-int bgzf_ref_block(const uint8_t *in, int n, uint8_t *out) {
+ * dynamic block does not fit (the caller then stores the block).  *st: which paths the block took
+ * (bgzf_ref.h), for the tests that build inputs on the encoder's edges. */
+int bgzf_ref_block_stats(const uint8_t *in, int n, uint8_t *out, bgzf_ref_stats *st) {
+    memset(st, 0, sizeof *st);
     static uint32_t table[1 << kHashBits];
     static int32_t cand[65536];
     memset(table, 0, sizeof table);
@@ -244,11 +263,18 @@ int bgzf_ref_block(const uint8_t *in, int n, uint8_t *out) {
             cand[p] = -1;
             if (p + 3 >= n) continue;
             cand[p] = (int32_t)table[hash4(in + p)] - 1;
+            int in_round = 0;
             for (int q = p - 1; q >= r0; q--)
                 if (memcmp(in + q, in + p, 4) == 0) {
                     cand[p] = q;
+                    in_round = 1;
                     break;
                 }
+            if (in_round) st->cand_round++;
+            else if (cand[p] >= 0) {
+                st->cand_table++;
+                if (memcmp(in + cand[p], in + p, 4) != 0) st->collisions++;
+            }
         }
         for (int p = r0; p < r1; p++)
             if (p + 3 < n) {
@@ -264,19 +290,30 @@ int bgzf_ref_block(const uint8_t *in, int n, uint8_t *out) {
         const int s1 = s0 + kSeg < n ? s0 + kSeg : n;
         for (int i = s0; i < s1;) {
             int bestl, bestd;
-            best_match(in, cand, i, s1, &bestl, &bestd);
+            best_match(in, cand, i, s1, &bestl, &bestd, st);
+            if (bestl >= kLazy && i + 1 < s1) st->lazy_skipped++;
             if (bestl >= 3 && bestl < kLazy && i + 1 < s1) {
                 int l2, d2;
-                best_match(in, cand, i + 1, s1, &l2, &d2);
-                if (l2 > bestl) bestl = 0;  /* a literal here, the longer match next */
+                best_match(in, cand, i + 1, s1, &l2, &d2, NULL);
+                if (l2 > bestl) {  /* a literal here, the longer match next */
+                    bestl = 0;
+                    st->lazy_deferrals++;
+                }
             }
             if (bestl >= 3) {
+                if (!st->matches || bestl < st->min_len) st->min_len = bestl;
+                if (bestl > st->max_len) st->max_len = bestl;
+                if (!st->matches || bestd < st->min_dist) st->min_dist = bestd;
+                if (bestd > st->max_dist) st->max_dist = bestd;
+                st->matches++;
+                if (bestl == s1 - i && bestl < 258) st->clipped++;
                 tok[nt++] = 0x80000000u | (uint32_t)bestl << 16 | (uint32_t)bestd;
                 lf[257 + len_code(bestl)]++;
                 df[dist_code(bestd)]++;
                 i += bestl;
             } else {
                 tok[nt++] = in[i];
+                st->literals++;
                 lf[in[i]]++;
                 i++;
             }
@@ -284,10 +321,11 @@ int bgzf_ref_block(const uint8_t *in, int n, uint8_t *out) {
     }
     lf[256]++;
     uint8_t ll[286], dl[30];
-    bgzf_huffman_lengths(lf, 286, 15, ll);
-    bgzf_huffman_lengths(df, 30, 15, dl);
+    st->retries_litlen = huffman_lengths(lf, 286, 15, ll, NULL);
+    st->retries_dist = huffman_lengths(df, 30, 15, dl, &st->dist_single);
     int used_d = 0;
     for (int i = 0; i < 30; i++) used_d |= dl[i] != 0;
+    st->dist_used = used_d;
     if (!used_d) dl[0] = 1;  /* no match: one distance code of length 1 (RFC 1951 3.2.7) */
     int hlit = 286;
     while (hlit > 257 && ll[hlit - 1] == 0) hlit--;
@@ -300,9 +338,12 @@ int bgzf_ref_block(const uint8_t *in, int n, uint8_t *out) {
     uint32_t cf[19] = {0};
     for (int i = 0; i < ns; i++) cf[sym[i]]++;
     uint8_t cl[19];
-    bgzf_huffman_lengths(cf, 19, 7, cl);
+    st->retries_codelen = huffman_lengths(cf, 19, 7, cl, NULL);
     int hclen = 19;
     while (hclen > 4 && cl[kClOrder[hclen - 1]] == 0) hclen--;
+    st->hlit = hlit;
+    st->hdist = hdist;
+    st->hclen = hclen;
     uint16_t lc[286], dc[30], cc[19];
     bgzf_canonical_codes(ll, 286, lc);
     bgzf_canonical_codes(dl, 30, dc);
@@ -346,4 +387,9 @@ int bgzf_ref_block(const uint8_t *in, int n, uint8_t *out) {
     for (int i = 0; i < 4; i++) out[18 + clen + i] = (uint8_t)(crc >> (8 * i));
     for (int i = 0; i < 4; i++) out[22 + clen + i] = (uint8_t)((uint32_t)n >> (8 * i));
     return bsize;
+}
+
+int bgzf_ref_block(const uint8_t *in, int n, uint8_t *out) {
+    bgzf_ref_stats st;
+    return bgzf_ref_block_stats(in, n, out, &st);
 }

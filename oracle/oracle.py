@@ -83,6 +83,8 @@ def load():
         lib.orc_check_agree.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
         lib.bgzf_ref_block.restype = C.c_int
         lib.bgzf_ref_block.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        lib.bgzf_ref_block_stats.restype = C.c_int
+        lib.bgzf_ref_block_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -340,6 +342,24 @@ def bgzf_block(data: bytes) -> bytes:
     out = np.zeros(65536, np.uint8)
     n = lib.bgzf_ref_block(src.ctypes.data, len(data), out.ctypes.data)
     return out[:n].tobytes()
+
+
+# bgzf_ref.h bgzf_ref_stats, field for field (int32 each)
+BGZF_STATS = ("retries_litlen", "retries_dist", "retries_codelen", "literals", "matches", "min_len", "max_len",
+              "min_dist", "max_dist", "clipped", "nice_stops", "lazy_deferrals", "lazy_skipped", "cand_round",
+              "cand_table", "collisions", "chain_cut_kchain", "chain_cut_maxdist", "hlit", "hdist", "hclen",
+              "dist_used", "dist_single")
+
+
+def bgzf_block_stats(data: bytes):
+    """bgzf_block(data) and the counters of the paths the block took (bgzf_ref.h bgzf_ref_stats)
+    -> (bytes, dict)."""
+    lib = load()
+    src = np.frombuffer(bytes(data) + b"\0" * 8, np.uint8)
+    out = np.zeros(65536, np.uint8)
+    st = np.zeros(len(BGZF_STATS), np.int32)
+    n = lib.bgzf_ref_block_stats(src.ctypes.data, len(data), out.ctypes.data, st.ctypes.data)
+    return out[:n].tobytes(), {k: int(v) for k, v in zip(BGZF_STATS, st)}
 
 
 class _HostSlot:
