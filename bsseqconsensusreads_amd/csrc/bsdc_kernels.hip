@@ -69,6 +69,12 @@ constexpr int kStageU = SMALL_STAGE_U;
 #ifndef SMALL_QDMA
 #define SMALL_QDMA 1  // k_small stages the quals with LDS-DMA (global_load_lds_dwordx4); 0: through VGPRs
 #endif
+#ifndef SMALL_CUTS
+// k_small's instruction cuts, one bit each (profiles/valu/README.md has every bit's A/B): 1 the
+// queue push's column bound in one mask and its empty rounds skipped, 2 the queue's three exp
+// terms by select, 4 an absent side's epilogue work skipped
+#define SMALL_CUTS 7
+#endif
 #ifndef LARGE_THREADS
 #define LARGE_THREADS 256  // k_large workgroup size (a multiple of 64)
 #endif
@@ -1467,19 +1473,20 @@ __device__ __forceinline__ void small_family(const KParams &P, const Tables *T, 
                         if (i < na) rev(rlu(dreg, o + i));
                     }
                 }
-                uint32_t bm[2], multi[2];
-#pragma unroll
-                for (int side = 0; side < 2; side++) {
-                    bm[side] = (mf[side] & 0x0F0F0F0Fu) | comp4(__builtin_bswap32(mr[side] & 0x0F0F0F0Fu));
-                    const uint32_t x = bm[side];
-                    multi[side] = x & ((x | 0x10101010u) - 0x01010101u);  // per byte: more than one base seen
-                }
+                // An absent side (hA / hB are wave-uniform) is skipped whole: its bm, multi, Qp and
+                // negm stay 0, and nothing below reads them -- resolve4 returns the present side's
+                // bytes, slowA / slowB are 0 for it, and the tag stores skip it.
+                uint32_t bm[2] = {0, 0}, multi[2] = {0, 0};
                 // per side and column: Q from the sum alone (valid when the column is not slow)
                 // (a sum of at most one unit per read of the set is a potential near tie with the
                 // unseen bases' 0: it takes the general path too)
                 uint32_t Qp[2] = {0, 0}, negm[2] = {0, 0};
 #pragma unroll
                 for (int side = 0; side < 2; side++) {
+                    if ((SMALL_CUTS & 4) && !(side == 0 ? hA : hB)) continue;
+                    bm[side] =(mf[side] & 0x0F0F0F0Fu) | comp4(__builtin_bswap32(mr[side] & 0x0F0F0F0Fu));
+                    const uint32_t x = bm[side];
+                    multi[side] = x & ((x | 0x10101010u) - 0x01010101u);  // per byte: more than one base seen
                     const int32_t nset = side == 0 ? cA : cB;
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
@@ -1501,7 +1508,9 @@ __device__ __forceinline__ void small_family(const KParams &P, const Tables *T, 
                 // rides in the column's output bytes (base | 0x10 if it is side B; qual 0 = none).
                 const uint32_t slowA = hA ? (bytes_nonzero(multi[0] & 0x7F7F7F7Fu) | negm[0]) & inA : 0u;
                 const uint32_t slowB = hB ? (bytes_nonzero(multi[1] & 0x7F7F7F7Fu) | negm[1]) & inB : 0u;
-                const uint32_t slow4 = slowA | slowB;
+                // only columns below lv are queued: the bytes past it are cleared here once (their
+                // output bytes are never read: the pack masks them, the tag rows end at ss_len)
+                const uint32_t slow4 = (slowA | slowB) & ((SMALL_CUTS & 1) ? ~bytes_past(8 * (lv - c), false) : ~0u);
                 if (slow4) {
                     const uint32_t useA = hA ? ~slowA : 0u, useB = (hB ? ~slowB : 0u) & ~useA;
                     const uint32_t fb = (ss[0] & useA) | ((ss[2] | 0x10101010u) & useB);
@@ -1511,8 +1520,9 @@ __device__ __forceinline__ void small_family(const KParams &P, const Tables *T, 
                 }
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
-                    const bool qd = ((slow4 >> (8 * j)) & 0xFFu) != 0 && c + j < lv;
+                    const bool qd = ((slow4 >> (8 * j)) & 0xFFu) != 0 && ((SMALL_CUTS & 1) || c + j < lv);
                     const uint64_t ms = ballot(qd);
+                    if ((SMALL_CUTS & 1) && ms == 0) continue;  // (wave-uniform) no lane has a slow column at this byte
                     if (qd) sq[nq + mbcnt(ms)] = (uint16_t)((e << 15) | (c + j));
                     nq += __builtin_popcountll(ms);
                 }
@@ -1592,11 +1602,21 @@ __device__ __forceinline__ void small_family(const KParams &P, const Tables *T, 
                 if (near_tie(D0, D1, D2, D3, best, ns))  // rare: fgbio's fp64 read-order pick
                     best = fp64_pick(SmallDesc{dlist + os}, ns, c, bimg, qimg, P.tab->lnc, P.tab->lne3);
                 const int32_t Db = best == 0 ? D0 : best == 1 ? D1 : best == 2 ? D2 : D3;
+                // The three other bases' differences in index order, picked by selects: `best` is
+                // per lane, so four `if (best != k)` blocks ran four exp bodies for three terms.
+                // Same terms, same order of the float additions (0 + x0 is exact): S is bit-identical.
+                const int32_t x0 = best == 0 ? D1 : D0, x1 = best <= 1 ? D2 : D1, x2 = best <= 2 ? D3 : D2;
                 float S = 0.0f;  // |D| < 2^30 here (<= 64 reads)
-                if (best != 0) S += term32(D0 - Db);
-                if (best != 1) S += term32(D1 - Db);
-                if (best != 2) S += term32(D2 - Db);
-                if (best != 3) S += term32(D3 - Db);
+                if (SMALL_CUTS & 2) {
+                    S = term32(x0 - Db);
+                    S += term32(x1 - Db);
+                    S += term32(x2 - Db);
+                } else {
+                    if (best != 0) S += term32(D0 - Db);
+                    if (best != 1) S += term32(D1 - Db);
+                    if (best != 2) S += term32(D2 - Db);
+                    if (best != 3) S += term32(D3 - Db);
+                }
                 const int Q = phred_of(S, thr);
                 const bool nocall = !(seen & 0x10u) || Q < P.qmin;  // no A/C/G/T read, or below the mask
                 vb = nocall ? kN : (1u << best);
