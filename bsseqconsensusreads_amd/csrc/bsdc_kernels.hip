@@ -38,43 +38,12 @@
 namespace {
 
 constexpr int kWave = 64;
-#ifndef SMALL_WAVES
-#define SMALL_WAVES 7  // k_small waves per SIMD the register budget is cut for (7: <= 64 VGPRs, <= 96 SGPRs)
-#endif
-#ifndef SMALL_SGPRS
-#define SMALL_SGPRS (SMALL_WAVES >= 8 ? 80 : 96)  // SGPR budget: <= 80 -> 8, <= 96 -> 7 waves per SIMD (MI355X_MICROARCH.md)
-#endif
+// The knobs below are numbers only (no alternative code behind them): a -D build through
+// BSDC_LIB_PATH is how the next A/B library is made.
 #ifndef SMALL_STAGE_U
 #define SMALL_STAGE_U 4  // k_small staging: image chunk loads in flight per lane
 #endif
 constexpr int kStageU = SMALL_STAGE_U;
-// Wave priority (s_setprio) while a wavefront issues its first global loads: from the kernel's table
-// loads until its family's reference-window loads are out, then back to 0 (profiles/r06/README.md,
-// prio/: C2 2.99 -> 2.93 ms, tag leg 3.39 -> 3.29).  The loads leave before other waves' LDS and VALU
-// work, so more of the HBM latency overlaps; holding the priority through the wait for the data
-// gains nothing, nor does the output pack at the raised priority.  1: from the family's metadata loads
-// on (about two thirds of the gain); 0: off.
-#ifndef SMALL_PRIO
-#define SMALL_PRIO 2
-#endif
-#ifndef SMALL_PRIO_LEVEL
-#define SMALL_PRIO_LEVEL 3  // the raised priority (1..3: 1 measured the same)
-#endif
-#ifndef SMALL_PRIO_END
-#define SMALL_PRIO_END 1  // where it drops back to 0: 0 after the image loads (less gain), 1 after the window loads, 2 after staging (no gain)
-#endif
-#ifndef LARGE_PRIO
-#define LARGE_PRIO 1  // k_large's staging loads issue at wave priority 3 (C3 -0.3%, C4 -1%; its convert's reference loads too, or from the kernel's entry, and k_join's table loads: no more); 0: off
-#endif
-#ifndef SMALL_QDMA
-#define SMALL_QDMA 1  // k_small stages the quals with LDS-DMA (global_load_lds_dwordx4); 0: through VGPRs
-#endif
-#ifndef SMALL_CUTS
-// k_small's instruction cuts, one bit each (profiles/valu/README.md has every bit's A/B): 1 the
-// queue push's column bound in one mask and its empty rounds skipped, 2 the queue's three exp
-// terms by select, 4 an absent side's epilogue work skipped
-#define SMALL_CUTS 7
-#endif
 #ifndef LARGE_THREADS
 #define LARGE_THREADS 256  // k_large workgroup size (a multiple of 64)
 #endif
@@ -109,12 +78,6 @@ constexpr int kOvlChunks = LARGE_OVL_CHUNKS;
 #define LARGE_OVL_U 2  // k_large overlap: tasks per thread whose loads are in flight together
 #endif
 constexpr int kOvlU = LARGE_OVL_U;
-#ifndef LARGE_OVL_BSTORE
-#define LARGE_OVL_BSTORE 1  // k_large overlap, mate b's unaligned whole dwords: 0 bytes, 1 one unaligned dword, 2 16-bit halves
-#endif
-#ifndef SMALL_OVL_BSTORE
-#define SMALL_OVL_BSTORE 1  // the same for k_small's overlap (overlap_dw): 0 bytes, 1 one unaligned dword
-#endif
 #ifndef LARGE_CONV_H
 #define LARGE_CONV_H 2  // k_large convert: SWAR dwords (4 positions each) per task, 1 or 2
 #endif
@@ -129,8 +92,12 @@ constexpr int kLConvU = LARGE_CONV_U;
 #endif
 constexpr int kLStageU = LARGE_STAGE_U;
 constexpr int kSmallMaxWaves = 8;              // wavefronts (families) per small-kernel workgroup, at most
-constexpr int kSmallMinWaves = SMALL_WAVES >= 8 ? 8 : 6;  // occupancy target the register budget is cut for
-constexpr int kSmallSimdWaves = SMALL_WAVES;   // waves per SIMD its registers allow
+// k_small's register budget is cut for 7 waves per SIMD: <= 64 VGPRs (launch bounds: 6 workgroups
+// of 8 waves per CU) and <= 96 SGPRs (amdgpu_num_sgpr).  The 8-wave budget (80 SGPRs) lost twice:
+// C2 3.08 -> 3.50 ms with VGPR spills, 3.18-3.21 ms with fewer staging loads (profiles/r04/ab_c/
+// README.md), and 3.09 against 2.94-2.95 ms with 54 SGPRs spilled (profiles/r06/README.md, r6zi).
+constexpr int kSmallMinWaves = 6;              // occupancy target the register budget is cut for
+constexpr int kSmallSimdWaves = 7;             // waves per SIMD its registers allow
 constexpr int kLdsBytes = 160 * 1024;           // LDS per CU
 constexpr double kLrScale = 1048576.0;          // 2^20
 constexpr int kSqBuckets = 136;                 // phred buckets of S: 4 per octave over [2^-32, 4)
@@ -178,7 +145,8 @@ __device__ __forceinline__ uint32_t comp_nt16(uint32_t b) { return __builtin_bit
 __device__ __forceinline__ bool is_acgt(uint32_t b) { return b != 0 && (b & (b - 1)) == 0 && b < 16; }
 __device__ __forceinline__ int acgt_idx(uint32_t b) { return __builtin_ctz(b); }
 
-__device__ __forceinline__ float det_expf(float x) {
+// (host too: make_tables tabulates the agreement case with the kernels' own arithmetic)
+__host__ __device__ __forceinline__ float det_expf(float x) {
     // keep in step with oracle/bsdc_oracle.c orc_det_expf: same reduction, same fma chain
     const float t = x * 1.44269504088896341f;
     const float n = rintf(t);
@@ -246,6 +214,37 @@ __device__ __forceinline__ bool near_tie(T d0, T d1, T d2, T d3, int best, int n
     if (best != 3 && d3 > sec) sec = d3;
     return (long long)m - (long long)sec <= (long long)nset;
 }
+// The single-strand call of one column from its four likelihood sums (int32_t: k_small, at most 64
+// reads, |D| < 2^30; long long: k_large, k_join) and `best`, the first maximum after the caller's
+// near-tie handling.  seen: a read shows an A/C/G/T there; n0..n3: its reads per base (only the
+// tags' depth / err use them).
+// S sums the three other bases' terms, their differences taken in index order by selects: `best`
+// is per lane, so four `if (best != k)` blocks ran four exp bodies for three terms.  Same terms,
+// same order of the float additions (0 + x0 is exact): S is bit-identical to that form.
+struct SsCall {
+    uint32_t base, qual;  // the call: (N, 2) without an A/C/G/T read or with Q below qmin
+    uint32_t depth, err;  // reads with an A/C/G/T, and those of them not showing the raw best base
+};
+template <typename T>
+__device__ __forceinline__ SsCall ss_call(T d0, T d1, T d2, T d3, int best, bool seen, uint32_t n0, uint32_t n1,
+                                          uint32_t n2, uint32_t n3, const float *thr, int qmin) {
+    auto e = [](T d) __attribute__((always_inline)) {  // the term by the sums' type
+        if constexpr (sizeof(T) == 4)
+            return term32(d);
+        else
+            return term(d);
+    };
+    const T db = best == 0 ? d0 : best == 1 ? d1 : best == 2 ? d2 : d3;
+    const T x0 = best == 0 ? d1 : d0, x1 = best <= 1 ? d2 : d1, x2 = best <= 2 ? d3 : d2;
+    float S = e(x0 - db);
+    S += e(x1 - db);
+    S += e(x2 - db);
+    const int Q = phred_of(S, thr);
+    const bool nocall = !seen || Q < qmin;
+    const uint32_t depth = n0 + n1 + n2 + n3;
+    const uint32_t nb = best == 0 ? n0 : best == 1 ? n1 : best == 2 ? n2 : n3;
+    return SsCall{nocall ? kN : 1u << best, nocall ? 2u : (uint32_t)Q, depth, depth - nb};
+}
 // fgbio's pick on a near tie: ConsensusBaseBuilder.add's four double-precision log-likelihood sums
 // (lnc for the read's base, lne3 for each other base), accumulated read by read in fgbio's read
 // order, then the first maximum by strict >.  That order is filterToMostCommonAlignment's output:
@@ -255,11 +254,10 @@ __device__ __forceinline__ bool near_tie(T d0, T d1, T d2, T d3, int best, int n
 // is found by selection: each step takes the smallest (length desc, address) key above the last.
 // Desc::get(i, addr, len, rev): the set's i-th read; its column col is image byte addr + col
 // (forward) or addr - col (reverse); bases at bimg, quals at qimg, same offsets.
-#ifndef FP64_PICK_ATTR
-#define FP64_PICK_ATTR  // (out of line, noinline: C2 k_small 3.065 -> 3.101 ms, profiles/r03/ab/README.md)
-#endif
+// (Left to the inliner: out of line, noinline, measured C2 k_small 3.065 -> 3.101 ms,
+// profiles/r03/ab/README.md.)
 template <class Desc>
-__device__ FP64_PICK_ATTR int fp64_pick(const Desc &ds, int n, int col, const uint8_t *bimg, const uint8_t *qimg, const double *lnc,
+__device__ int fp64_pick(const Desc &ds, int n, int col, const uint8_t *bimg, const uint8_t *qimg, const double *lnc,
                          const double *lne3) {
     double L0 = 0.0, L1 = 0.0, L2 = 0.0, L3 = 0.0;
     uint64_t lo = 0;
@@ -642,7 +640,6 @@ __device__ __forceinline__ void glds16(const uint8_t *g, uint8_t *lds) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
                                      (__attribute__((address_space(3))) void *)lds, 16, 0, 0);
 }
-__device__ __forceinline__ void st16(uint8_t *p, uint16_t v) { *reinterpret_cast<uint16_t *>(p) = v; }  // 2-aligned p
 // The LDS dword at any byte offset p of `base` (16-aligned) from two aligned loads and a byte
 // align: gfx950 LDS stalls an unaligned dword access (SQ_LDS_UNALIGNED_STALL)
 __device__ __forceinline__ uint32_t lds_any32(const uint8_t *base, int32_t p) {
@@ -692,7 +689,9 @@ __device__ __forceinline__ Ovl4 ovl4_compute(const Ovl4 &in4, int rem) {
 // holds overlap positions 4d - (xa & 3) .. + 3 (the overlap is ovl positions from xa in a and xb
 // in b).  a's bases and quals are loaded as aligned dwords (and stored so when the dword lies
 // inside the overlap); b's come from two aligned loads each and go back byte by byte, only inside
-// the overlap (a dword store when b is aligned too and the dword is whole): gfx950 stalls unaligned LDS accesses.
+// the overlap, or as one dword when the dword is whole: gfx950 stalls unaligned LDS accesses
+// (DESIGN.md 5.2), yet one unaligned ds_write_b32 beat four byte stores (C2 k_small 3.072 -> 3.046
+// ms, C3 k_large 8.55 -> 8.29: DESIGN.md 5.2, profiles/r02/ab/ ab_small2_* / ab_large7_*).
 __device__ __forceinline__ void overlap_dw(uint8_t *bimg, uint8_t *qimg, uint32_t xa, uint32_t xb, int ovl, int d) {
     const int p0 = 4 * d - (int)(xa & 3u);
     const uint32_t A0 = (xa & ~3u) + 4u * (uint32_t)d;
@@ -716,11 +715,9 @@ __device__ __forceinline__ void overlap_dw(uint8_t *bimg, uint8_t *qimg, uint32_
     if (whole && (B0 & 3) == 0) {
         st32(bimg + B0, o.y);
         st32(qimg + B0, o.qb);
-#if SMALL_OVL_BSTORE == 1
     } else if (whole) {  // b's unaligned dword: one unaligned ds_write_b32 each (fewer LDS ops than 4 bytes)
         stu32(bimg + B0, o.y);
         stu32(qimg + B0, o.qb);
-#endif
     } else {  // b's partial dword: bytes (b's bytes just outside the overlap may precede b's slot)
         for (int k = lo; k < hi; k++) {
             bimg[B0 + k] = (uint8_t)(o.y >> (8 * k));
@@ -762,24 +759,9 @@ __device__ __forceinline__ void ovl_dw_store(uint8_t *bimg, uint8_t *qimg, const
     if (whole && (t.B0 & 3) == 0) {
         st32(bimg + t.B0, o.y);
         st32(qimg + t.B0, o.qb);
-#if LARGE_OVL_BSTORE == 1
     } else if (whole) {  // b's unaligned dword: one unaligned ds_write_b32 each
         stu32(bimg + t.B0, o.y);
         stu32(qimg + t.B0, o.qb);
-#elif LARGE_OVL_BSTORE == 2
-    } else if (whole && (t.B0 & 1) == 0) {  // b's dword on a 2-byte boundary: two ds_write_b16 each
-        st16(bimg + t.B0, (uint16_t)o.y);
-        st16(bimg + t.B0 + 2, (uint16_t)(o.y >> 16));
-        st16(qimg + t.B0, (uint16_t)o.qb);
-        st16(qimg + t.B0 + 2, (uint16_t)(o.qb >> 16));
-    } else if (whole) {  // odd: byte, 16-bit, byte
-        bimg[t.B0] = (uint8_t)o.y;
-        st16(bimg + t.B0 + 1, (uint16_t)(o.y >> 8));
-        bimg[t.B0 + 3] = (uint8_t)(o.y >> 24);
-        qimg[t.B0] = (uint8_t)o.qb;
-        st16(qimg + t.B0 + 1, (uint16_t)(o.qb >> 8));
-        qimg[t.B0 + 3] = (uint8_t)(o.qb >> 24);
-#endif
     } else {
         for (int k = t.lo; k < t.hi; k++) {
             bimg[t.B0 + k] = (uint8_t)(o.y >> (8 * k));
@@ -950,7 +932,6 @@ __device__ __forceinline__ void small_family(const KParams &P, const Tables *T, 
     // reference windows.  Metadata loads go first so the window loads (whose addresses they hold)
     // are issued while the image chunks are still in flight; up to 4 chunk loads per lane per
     // round ----
-    if (SMALL_PRIO == 1) __builtin_amdgcn_s_setprio(SMALL_PRIO_LEVEL);
     const bool has = t < n;
     uint4 rc = make_uint4(0, 0, 0, 0);
     uint2 win = make_uint2(0, 0);
@@ -963,44 +944,32 @@ __device__ __forceinline__ void small_family(const KParams &P, const Tables *T, 
     const int nqc = (int)(img >> 4), nch = nqc + (int)(img >> 5);  // qual chunks, + packed-base chunks
     uint8_t *bimg = A;          // SmallLayout: bimg = 0, qimg = img
     uint8_t *qimg = A + img;
-    auto load_img = [&](int k) {
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (k < nqc)
-            v = *reinterpret_cast<const uint4 *>(B.qual + base_g + 16 * (uint32_t)k);
-        else if (k < nch)
-            v = *reinterpret_cast<const uint4 *>(B.seq + (base_g >> 1) + 16 * (uint32_t)(k - nqc));
-        return v;
-    };
     uint32_t qor = 0;  // OR of every qual byte this lane stages (0x80 set: a qual >= 128)
-#if SMALL_QDMA
-    // quals straight into LDS: one 1 KiB wave-instruction per 64 chunks, no VGPR round trip (the
-    // image is as contiguous in LDS as in HBM); the qual >= 128 test then reads them back
+    // quals straight into LDS (LDS-DMA, global_load_lds_dwordx4): one 1 KiB wave-instruction per 64
+    // chunks, no VGPR round trip (the image is as contiguous in LDS as in HBM); the qual >= 128
+    // test then reads them back.  Through VGPRs like the bases: C2 3.09-3.10 against 3.03-3.06 ms
+    // (profiles/r05/README.md, ab_qdma/).
     for (int u = 0; u < ((nqc + 63) >> 6); u++) {
         const int k = t + 64 * u;
         if (k < nqc) glds16(B.qual + base_g + 16u * (uint32_t)k, qimg + 1024 * u);
     }
-#endif
-    auto store_img = [&](int k, uint4 v) {
-        if (k < nqc && !SMALL_QDMA) {
-            *reinterpret_cast<uint4 *>(qimg + 16 * k) = v;
-            qor |= v.x | v.y | v.z | v.w;
-        } else if (k >= nqc && k < nch) {
-            unpack32<true>(v, bimg + 32 * (k - nqc));
-        }
+    // the packed-base chunks (image chunks nqc .. nch - 1) go through VGPRs, unpacked to flagged
+    // bytes on the way: a lane's chunk of round u is nqc + t + 64 u, or nch (none) past the last
+    auto load_img = [&](int k) {
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (k < nch) v = *reinterpret_cast<const uint4 *>(B.seq + (base_g >> 1) + 16 * (uint32_t)(k - nqc));
+        return v;
     };
-    // lanes take qual chunks and packed-base chunks in separate rounds (the unpack runs once per
-    // round of base chunks instead of in every round where some lane has one): chunk k of round u
-    // is qual chunk t + 64 u for u < uq, packed-base chunk t + 64 (u - uq) after
-    const int uq = SMALL_QDMA ? 0 : (nqc + 63) >> 6;
+    auto store_img = [&](int k, uint4 v) {
+        if (k < nch) unpack32<true>(v, bimg + 32 * (k - nqc));
+    };
     auto kmap = [&](int u) {
-        if (u < uq) return t + 64 * u < nqc ? t + 64 * u : nch;
-        const int kb = t + 64 * (u - uq);
+        const int kb = t + 64 * u;
         return kb < nch - nqc ? nqc + kb : nch;
     };
     uint4 v[kStageU];
 #pragma unroll
     for (int u = 0; u < kStageU; u++) v[u] = load_img(kmap(u));
-    if (SMALL_PRIO && SMALL_PRIO_END == 0) __builtin_amdgcn_s_setprio(0);
 
     const uint32_t gslot = rc.x;
     int32_t pos = (int32_t)rc.y;
@@ -1052,11 +1021,11 @@ __device__ __forceinline__ void small_family(const KParams &P, const Tables *T, 
     uint4 wv[2];
 #pragma unroll
     for (int u = 0; u < 2; u++) wv[u] = load_win(t + 64 * u);
-    if (SMALL_PRIO && SMALL_PRIO_END == 1) __builtin_amdgcn_s_setprio(0);  // (every first-round load is issued)
+    __builtin_amdgcn_s_setprio(0);  // every first-round load is issued (k_small raised it at its entry)
 #pragma unroll
     for (int u = 0; u < kStageU; u++) store_img(kmap(u), v[u]);
     const int ub = (nch - nqc + 63) >> 6;  // rounds of base chunks
-    for (int u0 = kStageU; u0 < uq + ub; u0 += kStageU) {  // families with more image chunks
+    for (int u0 = kStageU; u0 < ub; u0 += kStageU) {  // families with more image chunks
 #pragma unroll
         for (int u = 0; u < kStageU; u++) v[u] = load_img(kmap(u0 + u));
 #pragma unroll
@@ -1070,16 +1039,13 @@ __device__ __forceinline__ void small_family(const KParams &P, const Tables *T, 
 #pragma unroll
         for (int u = 0; u < 2; u++) store_win(k0 + t + 64 * u, wv[u]);
     }
-#if SMALL_QDMA
     __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the DMA'd quals have landed
     wave_sync();
     for (int k = t; k < nqc; k += 64) {
         const uint4 q = *reinterpret_cast<const uint4 *>(qimg + 16 * k);
         qor |= q.x | q.y | q.z | q.w;
     }
-#endif
     wave_sync();
-    if (SMALL_PRIO && SMALL_PRIO_END == 2) __builtin_amdgcn_s_setprio(0);
     if (stop == 1) return;
 
     // ---- tool 1: every converted record at once -- 16 lanes per record, 4 positions per lane per
@@ -1475,7 +1441,9 @@ __device__ __forceinline__ void small_family(const KParams &P, const Tables *T, 
                 }
                 // An absent side (hA / hB are wave-uniform) is skipped whole: its bm, multi, Qp and
                 // negm stay 0, and nothing below reads them -- resolve4 returns the present side's
-                // bytes, slowA / slowB are 0 for it, and the tag stores skip it.
+                // bytes, slowA / slowB are 0 for it, and the tag stores skip it.  (This skip, the one
+                // mask of the queue push below and the queue's terms by select: C2 2.936 -> 2.878 ms
+                // together, each one's A/B in profiles/valu/README.md.)
                 uint32_t bm[2] = {0, 0}, multi[2] = {0, 0};
                 // per side and column: Q from the sum alone (valid when the column is not slow)
                 // (a sum of at most one unit per read of the set is a potential near tie with the
@@ -1483,7 +1451,7 @@ __device__ __forceinline__ void small_family(const KParams &P, const Tables *T, 
                 uint32_t Qp[2] = {0, 0}, negm[2] = {0, 0};
 #pragma unroll
                 for (int side = 0; side < 2; side++) {
-                    if ((SMALL_CUTS & 4) && !(side == 0 ? hA : hB)) continue;
+                    if (!(side == 0 ? hA : hB)) continue;
                     bm[side] =(mf[side] & 0x0F0F0F0Fu) | comp4(__builtin_bswap32(mr[side] & 0x0F0F0F0Fu));
                     const uint32_t x = bm[side];
                     multi[side] = x & ((x | 0x10101010u) - 0x01010101u);  // per byte: more than one base seen
@@ -1510,7 +1478,7 @@ __device__ __forceinline__ void small_family(const KParams &P, const Tables *T, 
                 const uint32_t slowB = hB ? (bytes_nonzero(multi[1] & 0x7F7F7F7Fu) | negm[1]) & inB : 0u;
                 // only columns below lv are queued: the bytes past it are cleared here once (their
                 // output bytes are never read: the pack masks them, the tag rows end at ss_len)
-                const uint32_t slow4 = (slowA | slowB) & ((SMALL_CUTS & 1) ? ~bytes_past(8 * (lv - c), false) : ~0u);
+                const uint32_t slow4 = (slowA | slowB) & ~bytes_past(8 * (lv - c), false);
                 if (slow4) {
                     const uint32_t useA = hA ? ~slowA : 0u, useB = (hB ? ~slowB : 0u) & ~useA;
                     const uint32_t fb = (ss[0] & useA) | ((ss[2] | 0x10101010u) & useB);
@@ -1520,9 +1488,9 @@ __device__ __forceinline__ void small_family(const KParams &P, const Tables *T, 
                 }
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
-                    const bool qd = ((slow4 >> (8 * j)) & 0xFFu) != 0 && ((SMALL_CUTS & 1) || c + j < lv);
+                    const bool qd = ((slow4 >> (8 * j)) & 0xFFu) != 0;
                     const uint64_t ms = ballot(qd);
-                    if ((SMALL_CUTS & 1) && ms == 0) continue;  // (wave-uniform) no lane has a slow column at this byte
+                    if (ms == 0) continue;  // (wave-uniform) no lane has a slow column at this byte
                     if (qd) sq[nq + mbcnt(ms)] = (uint16_t)((e << 15) | (c + j));
                     nq += __builtin_popcountll(ms);
                 }
@@ -1601,34 +1569,15 @@ __device__ __forceinline__ void small_family(const KParams &P, const Tables *T, 
                 int best = first_max4(D0, D1, D2, D3);
                 if (near_tie(D0, D1, D2, D3, best, ns))  // rare: fgbio's fp64 read-order pick
                     best = fp64_pick(SmallDesc{dlist + os}, ns, c, bimg, qimg, P.tab->lnc, P.tab->lne3);
-                const int32_t Db = best == 0 ? D0 : best == 1 ? D1 : best == 2 ? D2 : D3;
-                // The three other bases' differences in index order, picked by selects: `best` is
-                // per lane, so four `if (best != k)` blocks ran four exp bodies for three terms.
-                // Same terms, same order of the float additions (0 + x0 is exact): S is bit-identical.
-                const int32_t x0 = best == 0 ? D1 : D0, x1 = best <= 1 ? D2 : D1, x2 = best <= 2 ? D3 : D2;
-                float S = 0.0f;  // |D| < 2^30 here (<= 64 reads)
-                if (SMALL_CUTS & 2) {
-                    S = term32(x0 - Db);
-                    S += term32(x1 - Db);
-                    S += term32(x2 - Db);
-                } else {
-                    if (best != 0) S += term32(D0 - Db);
-                    if (best != 1) S += term32(D1 - Db);
-                    if (best != 2) S += term32(D2 - Db);
-                    if (best != 3) S += term32(D3 - Db);
-                }
-                const int Q = phred_of(S, thr);
-                const bool nocall = !(seen & 0x10u) || Q < P.qmin;  // no A/C/G/T read, or below the mask
-                vb = nocall ? kN : (1u << best);
-                vq = nocall ? 2u : (uint32_t)Q;
+                const SsCall sc = ss_call(D0, D1, D2, D3, best, (seen & 0x10u) != 0, n0, n1, n2, n3, thr, P.qmin);
+                vb = sc.base;
+                vq = sc.qual;
                 if (TAGS) {  // this side's single-strand column (the fused tag statistics)
-                    const uint32_t depth = n0 + n1 + n2 + n3;
-                    const uint32_t nb = best == 0 ? n0 : best == 1 ? n1 : best == 2 ? n2 : n3;
                     const int64_t at = (4 * (int64_t)fam + s) * stride + c;
                     P.O.ss_base[at] = (uint8_t)vb;
                     P.O.ss_qual[at] = (uint8_t)vq;
-                    P.O.ss_depth[at] = (uint8_t)depth;  // (<= 64 reads)
-                    P.O.ss_err[at] = (uint8_t)(depth - nb);
+                    P.O.ss_depth[at] = (uint8_t)sc.depth;  // (<= 64 reads)
+                    P.O.ss_err[at] = (uint8_t)sc.err;
                 }
             }
             const uint32_t pb = (uint32_t)__shfl_xor((int)vb, 1, kWave), pq = (uint32_t)__shfl_xor((int)vq, 1, kWave);
@@ -1683,12 +1632,18 @@ __device__ __forceinline__ void small_family(const KParams &P, const Tables *T, 
 // One wavefront per family, the grid covering the size class's list (persistent waves taking
 // families from a counter measured 4.4x slower: the loop costs registers).
 template <bool TAGS>
-__global__ __launch_bounds__(kWave *kSmallMaxWaves, kSmallMinWaves) __attribute__((amdgpu_num_sgpr(SMALL_SGPRS))) void k_small(
+__global__ __launch_bounds__(kWave *kSmallMaxWaves, kSmallMinWaves) __attribute__((amdgpu_num_sgpr(96))) void k_small(
     KParams P, const uint32_t *fams, int64_t nfams, int32_t arena) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];  // the wavefronts' arenas
     __shared__ __attribute__((aligned(16))) Tables s_tab;           // static: its address folds into offsets
     if (((P.mode >> BSDC_MODE_STOP_SHIFT) & 15) == 15) return;  // profiling: launch cost alone
-    if (SMALL_PRIO == 2) __builtin_amdgcn_s_setprio(SMALL_PRIO_LEVEL);  // (from the table loads on)
+    // Wave priority 3 while the wavefront issues its first global loads: from the table loads here
+    // until its family's reference-window loads are out (small_family drops it to 0 there).  The
+    // loads leave before other waves' LDS and VALU work, so more of the HBM latency overlaps: C2
+    // 2.99 -> 2.93 ms, tag leg 3.39 -> 3.29 (profiles/r06/README.md, prio/).  Raised only from the
+    // family's metadata loads on: two thirds of the gain; priority 1: the same; dropped after the
+    // image loads already: less; held through staging or raised again for the output pack: no more.
+    __builtin_amdgcn_s_setprio(3);
     // (the tables by LDS-DMA with the barrier at the end of staging measured the same, 2.937 against
     // 2.940 ms: profiles/r06/prio/)
     load_tables<kTabBytes>(&P.tab->t, reinterpret_cast<uint8_t *>(&s_tab));
@@ -1926,13 +1881,13 @@ __device__ void process_large(const KParams &P, uint8_t *A, uint8_t *s_tab, cons
         }
     };
     // (quals by LDS-DMA here measured slower: profiles/r05/README.md)
-    auto chunk_of = [&](int i) { return i; };
-    const int nreg = nch;
     uint4 v[kLStageU];
-    if (LARGE_PRIO) __builtin_amdgcn_s_setprio(3);
+    // the staging loads issue at wave priority 3: C3 -0.3%, C4 -1% (profiles/r06/README.md); the
+    // convert's reference loads too, or from the kernel's entry, or k_join's table loads: no more
+    __builtin_amdgcn_s_setprio(3);
 #pragma unroll
     for (int u = 0; u < kLStageU; u++)
-        if (tt + u * G < nreg) v[u] = load_chunk(chunk_of(tt + u * G));
+        if (tt + u * G < nch) v[u] = load_chunk(tt + u * G);
     uint4 tv = make_uint4(0, 0, 0, 0);
     if (tt < kTabBytesL / 16) tv = reinterpret_cast<const uint4 *>(&P.tab->t)[tt];
     int c = 0, ml = 0;
@@ -1967,19 +1922,19 @@ __device__ void process_large(const KParams &P, uint8_t *A, uint8_t *s_tab, cons
     }
 #pragma unroll
     for (int u = 0; u < kLStageU; u++)
-        if (tt + u * G < nreg) store_chunk(chunk_of(tt + u * G), v[u]);
+        if (tt + u * G < nch) store_chunk(tt + u * G, v[u]);
     if (tt < kTabBytesL / 16) reinterpret_cast<uint4 *>(s_tab)[tt] = tv;
-    for (int k0 = tt + kLStageU * G; k0 < nreg; k0 += kLStageU * G) {  // families of more chunks
+    for (int k0 = tt + kLStageU * G; k0 < nch; k0 += kLStageU * G) {  // families of more chunks
 #pragma unroll
         for (int u = 0; u < kLStageU; u++)
-            if (k0 + u * G < nreg) v[u] = load_chunk(chunk_of(k0 + u * G));
+            if (k0 + u * G < nch) v[u] = load_chunk(k0 + u * G);
 #pragma unroll
         for (int u = 0; u < kLStageU; u++)
-            if (k0 + u * G < nreg) store_chunk(chunk_of(k0 + u * G), v[u]);
+            if (k0 + u * G < nch) store_chunk(k0 + u * G, v[u]);
     }
     int cops, maxlen_f;
     block_sum_max<G>(c, ml, red, cops, maxlen_f);  // (its barrier publishes the arena and the tables)
-    if (LARGE_PRIO) __builtin_amdgcn_s_setprio(0);  // (dropping it before the record metadata loop: C3 8.59 against 8.54 ms)
+    __builtin_amdgcn_s_setprio(0);  // (dropping it before the record metadata loop: C3 8.59 against 8.54 ms)
     const ArenaLayout Lo(n, 2 * (int64_t)img, maxlen_f, cops);
     uint16_t *lists = reinterpret_cast<uint16_t *>(A + Lo.lists);
     uint8_t *ssb = A + Lo.ssb;
@@ -2383,22 +2338,13 @@ __device__ void process_large(const KParams &P, uint8_t *A, uint8_t *s_tab, cons
         int best = first_max4(D0, D1, D2, D3);
         if (near_tie(D0, D1, D2, D3, best, pick4<PART>(cnt, s)))  // rare: fgbio's fp64 read-order pick
             best = fp64_pick(LargeDesc{desc + pick4<PART>(soff, s)}, pick4<PART>(cnt, s), col, slots, qimg, P.tab->lnc, P.tab->lne3);
-        const long long Db = best == 0 ? D0 : best == 1 ? D1 : best == 2 ? D2 : D3;
-        float S = 0.0f;
-        if (best != 0) S += term(D0 - Db);
-        if (best != 1) S += term(D1 - Db);
-        if (best != 2) S += term(D2 - Db);
-        if (best != 3) S += term(D3 - Db);
-        const int Q = phred_of(S, thr);
         // pass A left the OR of the column's A/C/G/T codes in ssb: 0 = no A/C/G/T read
-        const bool nocall = ssb[s * ssw + col] == 0 || Q < P.qmin;
-        ssb[s * ssw + col] = nocall ? (uint8_t)kN : (uint8_t)(1u << best);
-        ssq[s * ssw + col] = nocall ? (uint8_t)2 : (uint8_t)Q;
-        if (TAGS) {  // the column's depth / errors (the raw best base's reads) for the consensus tags
-            const uint32_t depth = (n01 & 0xFFFFu) + (n01 >> 16) + (n23 & 0xFFFFu) + (n23 >> 16);
-            const uint32_t nb = ((best < 2 ? n01 : n23) >> (16 * (best & 1))) & 0xFFFFu;
-            put_ss_stats(P, fam, s, col, depth, depth - nb);
-        }
+        const SsCall sc = ss_call(D0, D1, D2, D3, best, ssb[s * ssw + col] != 0, n01 & 0xFFFFu, n01 >> 16, n23 & 0xFFFFu,
+                                  n23 >> 16, thr, P.qmin);
+        ssb[s * ssw + col] = (uint8_t)sc.base;
+        ssq[s * ssw + col] = (uint8_t)sc.qual;
+        // the column's depth / errors (the raw best base's reads) for the consensus tags
+        if (TAGS) put_ss_stats(P, fam, s, col, sc.depth, sc.err);
     };
     // PART: a multi-base column's per-base sums (int32: a part holds < 255 reads a set) and counts
     // (PART) pass B's marked columns are the multi-base ones; the k-th of set s leaves its four
@@ -2912,21 +2858,11 @@ __device__ void join_family(const KParams &P, uint4 e0, uint4 e1, uint8_t *rows,
             *s_tie = 1;
             continue;
         }
-        const long long Db = best == 0 ? D0 : best == 1 ? D1 : best == 2 ? D2 : D3;
-        float S = 0.0f;
-        if (best != 0) S += term(D0 - Db);
-        if (best != 1) S += term(D1 - Db);
-        if (best != 2) S += term(D2 - Db);
-        if (best != 3) S += term(D3 - Db);
-        const int Q = phred_of(S, T.thr);
-        const uint32_t depth = n0 + n1 + n2 + n3;  // (without TAGS: nonzero iff a read shows an A/C/G/T)
-        const bool nocall = depth == 0 || Q < P.qmin;
-        ssb[s * pitch + c] = nocall ? (uint8_t)kN : (uint8_t)(1u << best);
-        ssq[s * pitch + c] = nocall ? (uint8_t)2 : (uint8_t)Q;
-        if (TAGS) {
-            const uint32_t nb = best == 0 ? n0 : best == 1 ? n1 : best == 2 ? n2 : n3;
-            put_ss_stats(P, e0.x, s, c, depth, depth - nb);
-        }
+        // (the counts' sum -- without TAGS, n0 alone: the OR -- is nonzero iff a read shows an A/C/G/T)
+        const SsCall sc = ss_call(D0, D1, D2, D3, best, n0 + n1 + n2 + n3 != 0, n0, n1, n2, n3, T.thr, P.qmin);
+        ssb[s * pitch + c] = (uint8_t)sc.base;
+        ssq[s * pitch + c] = (uint8_t)sc.qual;
+        if (TAGS) put_ss_stats(P, e0.x, s, c, sc.depth, sc.err);
     }
     __syncthreads();
     if (*s_tie) {  // (rare) the whole family in its HBM arena, fgbio's pick on the near ties
@@ -2963,9 +2899,9 @@ __global__ __launch_bounds__(kJoinThreads, 1024 / kJoinThreads) void k_join(KPar
 // ------------------------------------------------------------------------------------------
 // C-ABI
 // ------------------------------------------------------------------------------------------
-#ifndef BSDC_FORK
-#define BSDC_FORK 1
-#endif
+// The bucket dispatches of one call fan out over side streams (all on the caller's stream: C2
+// 3.02-3.03 against 2.98-2.99 ms, C4 6.37 against 5.60-5.63, profiles/r06/README.md streams/;
+// DESIGN.md 5.4).
 #ifndef BSDC_FORK_STREAMS
 #define BSDC_FORK_STREAMS 4
 #endif
@@ -2979,30 +2915,15 @@ struct bsdc_ctx {
     uint8_t *ref_seq = nullptr;
     int64_t ref_nibbles = 0;
     std::string err;
-    // (BSDC_FORK) side streams the bucket dispatches of one call fan out to, joined back to the
+    // side streams the bucket dispatches of one call fan out to, joined back to the
     // caller's stream by events, so one dispatch's tail overlaps the next
     hipStream_t side[kForkStreams] = {};
     hipEvent_t ev_fork = nullptr, ev_join[kForkStreams] = {};
 };
 
-static float det_expf_host(float x) {
-    const float tq = x * 1.44269504088896341f;
-    const float n = rintf(tq);
-    float r = fmaf(n, -6.93145751953125e-1f, x);
-    r = fmaf(n, -1.428606765330187e-6f, r);
-    float p = 1.38888889e-3f;
-    p = fmaf(p, r, 8.33333333e-3f);
-    p = fmaf(p, r, 4.16666667e-2f);
-    p = fmaf(p, r, 1.66666667e-1f);
-    p = fmaf(p, r, 0.5f);
-    p = fmaf(p, r, 1.0f);
-    p = fmaf(p, r, 1.0f);
-    return ldexpf(p, (int)n);
-}
-
 static int phred_agree(int64_t D, const float *thr) {
     const float x = (float)((double)(-D) * 9.5367431640625e-07);
-    const float e = x < -80.0f ? 0.0f : det_expf_host(x);
+    const float e = x < -80.0f ? 0.0f : det_expf(x);
     const float S = ((0.0f + e) + e) + e;
     int Q = 0;
     for (int k = 1; k < 94; k++) {
@@ -3101,6 +3022,31 @@ static void make_fp64(double post, double *lnc, double *lne3) {
             return BSDC_EDEVICE;                                                              \
         }                                                                                     \
     } while (0)
+
+// The launches: one helper per kernel; BSDC_MODE_TAGS picks the instance at run time (`n` entries
+// of `fams`, one workgroup each -- k_small: `nw` families a workgroup)
+static void launch_small(bool tags, int nw, size_t lds, hipStream_t s, const KParams &P, const uint32_t *fams, int64_t n,
+                         int32_t arena) {
+    const dim3 grid((unsigned)((n + nw - 1) / nw)), block(kWave * nw);
+    if (tags)
+        hipLaunchKernelGGL(k_small<true>, grid, block, lds, s, P, fams, n, arena);
+    else
+        hipLaunchKernelGGL(k_small<false>, grid, block, lds, s, P, fams, n, arena);
+}
+template <bool IN_LDS, int G, bool PART = false>
+static void launch_large(bool tags, size_t lds, hipStream_t s, const KParams &P, const uint4 *fams, int64_t n, int32_t arena,
+                         int64_t scratch_off) {
+    if (tags)
+        hipLaunchKernelGGL((k_large<IN_LDS, G, true, PART>), dim3((unsigned)n), dim3(G), lds, s, P, fams, n, arena, scratch_off);
+    else
+        hipLaunchKernelGGL((k_large<IN_LDS, G, false, PART>), dim3((unsigned)n), dim3(G), lds, s, P, fams, n, arena, scratch_off);
+}
+static void launch_join(bool tags, size_t lds, hipStream_t s, const KParams &P, const uint4 *sfams, int64_t n) {
+    if (tags)
+        hipLaunchKernelGGL(k_join<true>, dim3((unsigned)n), dim3(kJoinThreads), lds, s, P, sfams, n);
+    else
+        hipLaunchKernelGGL(k_join<false>, dim3((unsigned)n), dim3(kJoinThreads), lds, s, P, sfams, n);
+}
 
 extern "C" {
 
@@ -3221,15 +3167,14 @@ int32_t bsdc_ctx_create(int32_t device, const bsdc_params *params, bsdc_ctx **ou
         bsdc_ctx_destroy(c);
         return BSDC_EDEVICE;
     }
-    if (BSDC_FORK) {  // the side streams and their events: all of them, or the context fails
-        bool ok = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess;
-        for (int i = 0; ok && i < kForkStreams; i++)
-            ok = hipStreamCreateWithFlags(&c->side[i], hipStreamNonBlocking) == hipSuccess &&
-                 hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming) == hipSuccess;
-        if (!ok) {
-            bsdc_ctx_destroy(c);
-            return BSDC_EDEVICE;
-        }
+    // the side streams and their events: all of them, or the context fails
+    bool ok = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess;
+    for (int i = 0; ok && i < kForkStreams; i++)
+        ok = hipStreamCreateWithFlags(&c->side[i], hipStreamNonBlocking) == hipSuccess &&
+             hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        bsdc_ctx_destroy(c);
+        return BSDC_EDEVICE;
     }
     *out = c;
     return 0;
@@ -3332,8 +3277,8 @@ int32_t bsdc_run(bsdc_ctx *c, const bsdc_family_batch *b, bsdc_consensus *o, int
     P.ref_chunks = ref_chunks(b->max_len);
     P.ref_chunks_inv = (uint32_t)((((uint64_t)1 << 32) + (uint64_t)P.ref_chunks - 1) / (uint64_t)P.ref_chunks);
     P.qmin = c->params.min_consensus_base_quality;
-    // the dispatches: on `s`, or (BSDC_FORK) spread over the side streams (created with the
-    // context) after an event on `s`
+    const bool tg = (mode & BSDC_MODE_TAGS) != 0;  // every launch takes its kernel's TAGS instance
+    // the dispatches: spread over the side streams (created with the context) after an event on `s`
     int nd = 0, used = 0;
     int32_t rc = 0;
     auto fail = [&](hipError_t e, const char *what) {
@@ -3341,7 +3286,6 @@ int32_t bsdc_run(bsdc_ctx *c, const bsdc_family_batch *b, bsdc_consensus *o, int
         rc = BSDC_EDEVICE;
     };
     auto next_stream = [&]() -> hipStream_t {
-        if (!BSDC_FORK) return s;
         hipError_t e;
         if (nd == 0 && (e = hipEventRecord(c->ev_fork, s)) != hipSuccess) {
             fail(e, "hipEventRecord(fork)");
@@ -3362,7 +3306,6 @@ int32_t bsdc_run(bsdc_ctx *c, const bsdc_family_batch *b, bsdc_consensus *o, int
     auto launch_split = [&]() {
         if (rc != 0 || b->n_split_parts <= 0 || b->n_split_fams <= 0) return;
         const int32_t a = b->split_part_arena;
-        const bool tg = (mode & BSDC_MODE_TAGS) != 0;
         const hipStream_t ls = next_stream();
         if (rc != 0) return;
         const uint4 *pf = reinterpret_cast<const uint4 *>(b->split_parts);
@@ -3372,24 +3315,13 @@ int32_t bsdc_run(bsdc_ctx *c, const bsdc_family_batch *b, bsdc_consensus *o, int
         // BSDC_MODE_VOTE (the tools-only launches dump tool-2 records and stop before it) or with a
         // profiling stop knob (the parts return early) that scratch is never written, so no join
         const bool join = (mode & BSDC_MODE_VOTE) && ((mode >> BSDC_MODE_STOP_SHIFT) & 15) == 0;
-        if (tg) {
-            hipLaunchKernelGGL((k_large<true, kLargeThreads, true, true>), dim3((unsigned)b->n_split_parts), dim3(kLargeThreads),
-                               (size_t)a, ls, P, pf, b->n_split_parts, a, (int64_t)0);
-            if (join)
-                hipLaunchKernelGGL((k_join<true>), dim3((unsigned)b->n_split_fams), dim3(kJoinThreads), jl, ls, P, sf,
-                                   b->n_split_fams);
-        } else {
-            hipLaunchKernelGGL((k_large<true, kLargeThreads, false, true>), dim3((unsigned)b->n_split_parts),
-                               dim3(kLargeThreads), (size_t)a, ls, P, pf, b->n_split_parts, a, (int64_t)0);
-            if (join)
-                hipLaunchKernelGGL((k_join<false>), dim3((unsigned)b->n_split_fams), dim3(kJoinThreads), jl, ls, P, sf,
-                                   b->n_split_fams);
-        }
+        launch_large<true, kLargeThreads, true>(tg, (size_t)a, ls, P, pf, b->n_split_parts, a, 0);
+        if (join) launch_join(tg, jl, ls, P, sf, b->n_split_fams);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) fail(e, "split launch");
     };
     auto launch_small_all = [&]() {
-    if (!(mode & BSDC_MODE_SKIP_SMALL) && rc == 0) {
+        if ((mode & BSDC_MODE_SKIP_SMALL) || rc != 0) return;
         const uint32_t *f = b->small_fams;
         for (int q = 0; q < BSDC_SMALL_BUCKETS && rc == 0; q++) {
             const int64_t nf = b->n_small[q];
@@ -3403,22 +3335,17 @@ int32_t bsdc_run(bsdc_ctx *c, const bsdc_family_batch *b, bsdc_consensus *o, int
                 const int64_t w8 = 8 * std::min<int64_t>(kSmallSimdWaves / 2, kLdsBytes / (kTabBytes + g2 + 8 * a));
                 const int nw = w8 > w4 ? 8 : 4;
                 const size_t lds = (size_t)nw * (size_t)a + (size_t)g2;  // + the static tables
-                const int64_t blocks = (nf + nw - 1) / nw;
                 const hipStream_t ls = next_stream();
                 if (rc) break;
-                if (mode & BSDC_MODE_TAGS)
-                    hipLaunchKernelGGL(k_small<true>, dim3((unsigned)blocks), dim3(kWave * nw), lds, ls, P, f, nf, b->small_arena[q]);
-                else
-                    hipLaunchKernelGGL(k_small<false>, dim3((unsigned)blocks), dim3(kWave * nw), lds, ls, P, f, nf, b->small_arena[q]);
+                launch_small(tg, nw, lds, ls, P, f, nf, b->small_arena[q]);
                 const hipError_t e = hipGetLastError();
                 if (e != hipSuccess) fail(e, "k_small launch");
             }
             f += 4 * nf;
         }
-    }
     };
     auto launch_large_all = [&]() {
-    if (!(mode & BSDC_MODE_SKIP_LARGE) && rc == 0) {
+        if ((mode & BSDC_MODE_SKIP_LARGE) || rc != 0) return;
         // one dispatch per non-empty bucket: its LDS arena size sets how many workgroups share a CU
         const uint4 *f = reinterpret_cast<const uint4 *>(b->large_fams);
         // every bucket beyond the LDS budget has its own region of `scratch` (the dispatches may
@@ -3431,28 +3358,12 @@ int32_t bsdc_run(bsdc_ctx *c, const bsdc_family_batch *b, bsdc_consensus *o, int
                 const bool big = q >= kLargeBigBucket;  // 3, 2 or 1 workgroups per CU, or HBM scratch
                 const hipStream_t ls = next_stream();
                 if (rc) break;
-                const bool tg = (mode & BSDC_MODE_TAGS) != 0;
                 if (a <= BSDC_LARGE_LDS_MAX && !big) {
-                    if (tg)
-                        hipLaunchKernelGGL((k_large<true, kLargeThreads, true>), dim3((unsigned)nf), dim3(kLargeThreads), (size_t)a, ls, P, f,
-                                           nf, a, (int64_t)0);
-                    else
-                        hipLaunchKernelGGL((k_large<true, kLargeThreads, false>), dim3((unsigned)nf), dim3(kLargeThreads), (size_t)a, ls, P,
-                                           f, nf, a, (int64_t)0);
+                    launch_large<true, kLargeThreads>(tg, (size_t)a, ls, P, f, nf, a, 0);
                 } else if (a <= BSDC_LARGE_LDS_MAX) {
-                    if (tg)
-                        hipLaunchKernelGGL((k_large<true, kLargeThreadsBig, true>), dim3((unsigned)nf), dim3(kLargeThreadsBig), (size_t)a, ls,
-                                           P, f, nf, a, (int64_t)0);
-                    else
-                        hipLaunchKernelGGL((k_large<true, kLargeThreadsBig, false>), dim3((unsigned)nf), dim3(kLargeThreadsBig), (size_t)a,
-                                           ls, P, f, nf, a, (int64_t)0);
+                    launch_large<true, kLargeThreadsBig>(tg, (size_t)a, ls, P, f, nf, a, 0);
                 } else {
-                    if (tg)
-                        hipLaunchKernelGGL((k_large<false, kLargeThreadsBig, true>), dim3((unsigned)nf), dim3(kLargeThreadsBig), 0, ls, P, f,
-                                           nf, a, soff);
-                    else
-                        hipLaunchKernelGGL((k_large<false, kLargeThreadsBig, false>), dim3((unsigned)nf), dim3(kLargeThreadsBig), 0, ls, P,
-                                           f, nf, a, soff);
+                    launch_large<false, kLargeThreadsBig>(tg, 0, ls, P, f, nf, a, soff);
                     soff += nf * (int64_t)a;
                 }
                 const hipError_t e = hipGetLastError();
@@ -3461,7 +3372,6 @@ int32_t bsdc_run(bsdc_ctx *c, const bsdc_family_batch *b, bsdc_consensus *o, int
             f += nf;
         }
         launch_split();  // (first instead: not faster, profiles/r05/README.md)
-    }
     };
     // small families first (the large families' dispatches first: not faster, profiles/r05/README.md)
     launch_small_all();

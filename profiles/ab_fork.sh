@@ -1,6 +1,9 @@
 #!/bin/bash
 # A/B of the side-stream fan-out (BSDC_FORK / BSDC_FORK_STREAMS builds under abl/): GPU parity of
-# the first library, then the C2 / C3 / C4 bench per library.  Usage: bash profiles/ab_fork.sh <tag> <lib.so>...
+# the first library, then the C2 / C3 / C4 bench per library.
+# (-DBSDC_FORK no longer exists in bsdc_kernels.hip: the side streams are the only path, and only
+# -DBSDC_FORK_STREAMS=<n> still makes a different library.)
+# Usage: bash profiles/ab_fork.sh <tag> <lib.so>...
 set -u -o pipefail
 TAG=$1; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
