@@ -26,6 +26,7 @@ from . import records as R
 
 LINK_MATE_NONE = 0xFFFF
 MAX_FAMILY_RECORDS = 0xFFFE  # BSDC_MAX_FAMILY_RECORDS: every in-family index stays below LINK_MATE_NONE
+MAX_FILTER_SLOTS = 65536  # BSDC_MAX_FILTER_SLOTS: the alignment filter's 16-bit slot offsets
 LINK_AB = 1 << 16
 LINK_BA = 1 << 17
 LINK_COMPLEX = 1 << 18
@@ -83,7 +84,7 @@ def small_arena_bytes(n, img, nconv, complex_ops, max_len):
     R = 2 * np.asarray(img, dtype=np.int64) + round16(4 * n) + 16 + round16(n)
     e_ref = R + np.asarray(nconv, dtype=np.int64) * ws
     simp = R + round16(16 * n) + round16(n) + 2 * round16(2 * n)
-    e_f = simp + np.where(cops > 0, round16(4 * (cops + 4 * n)) + 256, 0)  # (+ filter_group's scratch)
+    e_f = simp + np.where(cops > 0, round16(4 * (cops + 4 * n)), 0)
     e_v = R + 8 * ow
     return np.maximum(np.maximum(e_ref, e_f), e_v)
 
@@ -96,7 +97,7 @@ def large_arena_bytes(n, slot_bytes, max_len, complex_ops):
     # ORs and read counts: 44 B per column (bsdc_layout::kVoteRegionPerCol)
     total = np.maximum(round16(n * 48) + round16(2 * n), 44 * ssw) + round16(n * 8) + 8 * ssw
     cops = np.asarray(complex_ops, dtype=np.int64)
-    total = total + np.where(cops > 0, round16(4 * (cops + 4 * n)) + 512, 0)  # (+ filter_group's scratch, X and Y)
+    total = total + np.where(cops > 0, round16(4 * (cops + 4 * n)), 0)
     total = total + round16(np.asarray(slot_bytes, dtype=np.int64))
     return total
 
@@ -914,6 +915,11 @@ def materialize_py(plan: FamilyPlan, f0: int, f1: int, small_cap: int = SMALL_AR
         np.maximum.at(max_len_f, fam_of, Lb)
     cops = np.bincount(fam_of, weights=cnt_c, minlength=nf)[:nf].astype(np.int64) if nr else np.zeros(nf, np.int64)
     nconv = np.bincount(fam_of, weights=convb.astype(np.int64), minlength=nf)[:nf].astype(np.int64) if nr else np.zeros(nf, np.int64)
+    # the filter's simplified-cigar slots: one per M-only record, ops + 2 per complex one
+    slots = np.bincount(fam_of, weights=np.where(complex_, nops + 2, 1), minlength=nf)[:nf] if nr else np.zeros(nf)
+    if ((cops > 0) & (slots > MAX_FILTER_SLOTS)).any():
+        raise ValueError("family whose alignment filter needs more than 65536 cigar slots "
+                         "(BSDC_MAX_FILTER_SLOTS: 16-bit slot offset)")
     need_s = small_arena_bytes(fam_sizes, img, nconv, cops, max_len)
     need_l = large_arena_bytes(fam_sizes, 2 * img, max_len_f, cops)
     small = (fam_sizes <= 64) & (need_s <= small_cap) & (img // 32 < (1 << 24))

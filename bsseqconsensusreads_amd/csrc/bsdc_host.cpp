@@ -702,17 +702,20 @@ int32_t bsdc_materialize_fill(bsdc_batch *b, const bsdc_batch_arrays *o, int64_t
     if (bad & 2) return fail(BSDC_EINVAL, "converting records needs the reference");
     if (bad & 4) return fail(BSDC_EINVAL, "reference too large for 32-bit nibble offsets");
     // ---- per family: offsets, list entry, arena needs, size class ----
-#pragma omp parallel for schedule(static)
+    int over_slots = 0;
+#pragma omp parallel for schedule(static) reduction(| : over_slots)
     for (int64_t f = 0; f < nf; f++) {
         const int64_t a = pv.fam_off[b->f0 + f] - b->r0, e = pv.fam_off[b->f0 + f + 1] - b->r0;
         const int64_t n = e - a;
-        int64_t cops = 0, nconv = 0, mlf = 0;
+        int64_t cops = 0, nconv = 0, mlf = 0, slots = 0;
         for (int64_t i = a; i < e; i++) {
             const int64_t k = pv.order[b->r0 + i];
             if (cplx[i]) cops += nops[i];
+            slots += cplx[i] ? nops[i] + 2 : 1;  // the filter's simplified-cigar slots (k_large's op bound)
             nconv += pv.conv[k] ? 1 : 0;
             mlf = std::max<int64_t>(mlf, pv.L[k]);
         }
+        if (cops > 0 && slots > BSDC_MAX_FILTER_SLOTS) over_slots |= 1;
         o->fam_off[f] = (uint32_t)a;
         const int64_t img = b->img[f];
         o->fam_entry[4 * f] = (uint32_t)f;
@@ -750,6 +753,9 @@ int32_t bsdc_materialize_fill(bsdc_batch *b, const bsdc_batch_arrays *o, int64_t
         }
         o->cls[f] = (int8_t)cls;
     }
+    if (over_slots)
+        return fail(BSDC_EINVAL, "family whose alignment filter needs more than 65536 cigar slots "
+                                 "(BSDC_MAX_FILTER_SLOTS: 16-bit slot offset)");
     o->fam_off[nf] = (uint32_t)nr;
     return 0;
 }

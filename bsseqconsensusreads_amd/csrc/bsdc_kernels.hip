@@ -493,10 +493,12 @@ __device__ __forceinline__ bool cigar_prefix(const uint32_t *ac, int an, const u
 
 // fgbio filterToMostCommonAlignment on one of X / Y, single thread.  `ord` (scratch, n entries)
 // holds the candidate records; srclen[] / sofs[] / so[] describe them; rejected ones get set 0xFF.
-// gdef / gsize: 64 u16 each of LDS scratch (arrays on the stack would give the whole kernel a
-// scratch allocation for this rare path)
+// isdef: cnt bytes of scratch, isdef[i] = ord[i] defines a group.  There is no group table, so a
+// set may hold as many groups as reads (fgbio has no cap): a read defines a group when it is a
+// prefix of no earlier definer, a group's size is the reads from its definer on that are
+// prefixes of it, and the first largest group wins.
 __device__ void filter_group(uint16_t *ord, int cnt, const uint16_t *srclen, const uint32_t *sofs, const uint32_t *so,
-                             uint8_t *set, uint16_t *gdef, uint16_t *gsize) {
+                             uint8_t *set, uint8_t *isdef) {
     if (cnt < 2) return;
     for (int i = 1; i < cnt; i++) {  // stable sort by source length, descending
         const uint16_t x = ord[i];
@@ -507,32 +509,30 @@ __device__ void filter_group(uint16_t *ord, int cnt, const uint16_t *srclen, con
         }
         ord[j + 1] = x;
     }
+    auto prefix = [&](int i, int d) {
+        const uint32_t ai = sofs[ord[i]], bi = sofs[ord[d]];
+        return cigar_prefix(so + (ai & 0xFFFF), (int)(ai >> 16), so + (bi & 0xFFFF), (int)(bi >> 16));
+    };
     int ng = 0;
     for (int i = 0; i < cnt; i++) {
-        const uint32_t ai = sofs[ord[i]];
         bool found = false;
-        for (int gi = 0; gi < ng; gi++) {
-            const uint32_t bi = sofs[gdef[gi]];
-            if (cigar_prefix(so + (ai & 0xFFFF), (int)(ai >> 16), so + (bi & 0xFFFF), (int)(bi >> 16))) {
-                gsize[gi]++;
-                found = true;
-            }
-        }
-        if (!found && ng < 64) {
-            gdef[ng] = ord[i];
-            gsize[ng] = 1;
-            ng++;
-        }
+        for (int d = 0; d < i && !found; d++) found = isdef[d] && prefix(i, d);
+        isdef[i] = !found;
+        ng += !found;
     }
     if (ng <= 1) return;
-    int best = 0;
-    for (int gi = 1; gi < ng; gi++)
-        if (gsize[gi] > gsize[best]) best = gi;
-    const uint32_t bi = sofs[gdef[best]];
-    for (int i = 0; i < cnt; i++) {
-        const uint32_t ai = sofs[ord[i]];
-        if (!cigar_prefix(so + (ai & 0xFFFF), (int)(ai >> 16), so + (bi & 0xFFFF), (int)(bi >> 16))) set[ord[i]] = 0xFF;
+    int best = 0, bsize = 0;
+    for (int d = 0; d < cnt; d++) {
+        if (!isdef[d]) continue;
+        int size = 0;
+        for (int i = d; i < cnt; i++) size += prefix(i, d);
+        if (size > bsize) {
+            bsize = size;
+            best = d;
+        }
     }
+    for (int i = 0; i < cnt; i++)
+        if (!prefix(i, best)) set[ord[i]] = 0xFF;
 }
 
 struct KParams {
@@ -1295,8 +1295,8 @@ __device__ __forceinline__ void small_family(const KParams &P, const Tables *T, 
         wave_sync();
         if (t == 0) {
             uint32_t *so = reinterpret_cast<uint32_t *>(A + Lo.simp);
-            uint16_t *grp = reinterpret_cast<uint16_t *>(A + Lo.grp);
             uint32_t *sofs = so + cops + 2 * n;
+            uint8_t *isdef = reinterpret_cast<uint8_t *>(sofs + n);  // (the region's last n words)
             uint32_t fill = 0;
             for (int r = 0; r < n; r++) {
                 sofs[r] = 0;
@@ -1317,7 +1317,7 @@ __device__ __forceinline__ void small_family(const KParams &P, const Tables *T, 
                     if (setv[r] == s1) ordv[cnt++] = (uint16_t)r;
                 for (int r = 0; r < n; r++)
                     if (setv[r] == s2) ordv[cnt++] = (uint16_t)r;
-                filter_group(ordv, cnt, srcl, sofs, so, setv, grp, grp + 64);
+                filter_group(ordv, cnt, srcl, sofs, so, setv, isdef);
             }
         }
         wave_sync();
@@ -1940,7 +1940,6 @@ __device__ void process_large(const KParams &P, uint8_t *A, uint8_t *s_tab, cons
     uint8_t *ssb = A + Lo.ssb;
     uint8_t *ssq = A + Lo.ssq;
     uint32_t *simp = reinterpret_cast<uint32_t *>(A + Lo.simp);
-    uint16_t *grp = reinterpret_cast<uint16_t *>(A + Lo.grp);  // filter_group scratch, X then Y (complex families)
     const int ssw = Lo.ssw;
     if (stop == 1) return;
 
@@ -2239,6 +2238,7 @@ __device__ void process_large(const KParams &P, uint8_t *A, uint8_t *s_tab, cons
         uint32_t *sofs = simp + cops + 2 * n;
         uint16_t *srcl = reinterpret_cast<uint16_t *>(simp + cops + 3 * n);  // n u16 in the last n words
         uint8_t *setv = reinterpret_cast<uint8_t *>(srcl + n);               // ... and n bytes after them
+        uint8_t *isdef = setv + n;  // ... and the last n: filter_group's definer marks, X from the front, Y from the back
         uint32_t run = 0;
         for (int base = 0; base < n; base += G) {
             const int r = base + tt;
@@ -2283,7 +2283,7 @@ __device__ void process_large(const KParams &P, uint8_t *A, uint8_t *s_tab, cons
                 if (setv[r] == s1) ord[c++] = (uint16_t)r;
             for (int r = 0; r < n; r++)
                 if (setv[r] == s2) ord[c++] = (uint16_t)r;
-            filter_group(ord, c, srcl, sofs, so, setv, grp + 128 * xy, grp + 128 * xy + 64);
+            filter_group(ord, c, srcl, sofs, so, setv, xy == 0 ? isdef : isdef + n - c);  // (X and Y share no record)
         }
         __syncthreads();
         for (int r = tt; r < n; r += G) M[r].set = setv[r];

@@ -67,6 +67,11 @@ typedef struct {
 #define BSDC_LINK_MATE_MASK 0xFFFFu   /* template mate (R2 of this R1) index within family; 0xFFFF = none */
 #define BSDC_MAX_FAMILY_RECORDS 65534 /* so every in-family index stays below 0xFFFF; the host planner
                                          (bsdc_materialize_prepare, batch.materialize_py) refuses larger families */
+/* The alignment filter keeps each source read's simplified cigar at a 16-bit offset into the
+   family's slots (one per M-only record, ops + 2 per complex record), so a family that holds a
+   complex cigar has at most this many: every offset is then below 65536.  The host planner
+   refuses a larger one, as above. */
+#define BSDC_MAX_FILTER_SLOTS 65536
 #define BSDC_LINK_AB (1u << 16)       /* MI ends in /A */
 #define BSDC_LINK_BA (1u << 17)       /* MI ends in /B */
 #define BSDC_LINK_COMPLEX (1u << 18)  /* cigar is not a single M-like run: read cig_* */

@@ -29,7 +29,7 @@ constexpr int kVoteRegionPerCol = 44;
 //   R           reference windows (staging, convert) | alignment-filter scratch (source reads) |
 //               duplex rows + queued columns (vote)
 struct SmallLayout {
-    uint32_t bimg, qimg, lists, misc, ref, meta, setv, ordv, srcl, simp, grp, outb, outq, squeue, total;
+    uint32_t bimg, qimg, lists, misc, ref, meta, setv, ordv, srcl, simp, outb, outq, squeue, total;
     int32_t ws, ow;
     BSDC_HD SmallLayout(int n, int64_t img, int nconv, int64_t cops, int max_len) {
         ws = 32 * ref_chunks(max_len);
@@ -51,8 +51,7 @@ struct SmallLayout {
         ordv = setv + (uint32_t)round16(n);
         srcl = ordv + (uint32_t)round16(2 * (int64_t)n);
         simp = srcl + (uint32_t)round16(2 * (int64_t)n);
-        grp = (uint32_t)((int64_t)simp + (cops > 0 ? round16(4 * (cops + 4 * (int64_t)n)) : 0));
-        const int64_t e_f = (int64_t)grp + (cops > 0 ? 256 : 0);  // filter_group's 2 x 64 u16
+        const int64_t e_f = (int64_t)simp + (cops > 0 ? round16(4 * (cops + 4 * (int64_t)n)) : 0);
         outb = (uint32_t)R;  // duplex bases, 2 ends
         outq = (uint32_t)(R + 2 * (int64_t)ow);
         squeue = (uint32_t)(R + 4 * (int64_t)ow);  // queued (end, column), u16: at most 2 ow of them
@@ -67,7 +66,7 @@ struct SmallLayout {
 // the kernel stages the image and writes the metadata before it knows the family's longest read
 // and cigar size (which place the regions after them).
 struct ArenaLayout {
-    uint32_t meta, clist, lists, ssb, ssq, simp, grp, slots, total;
+    uint32_t meta, clist, lists, ssb, ssq, simp, slots, total;
     int32_t ssw;
     BSDC_HD ArenaLayout(int n, int64_t slot_bytes, int max_len, int64_t complex_ops) {
         ssw = (int32_t)round16(max_len + 2);
@@ -89,8 +88,6 @@ struct ArenaLayout {
         o += 4 * (int64_t)ssw;
         simp = (uint32_t)o;
         if (complex_ops > 0) o += round16(4 * (complex_ops + 4 * (int64_t)n));
-        grp = (uint32_t)o;  // filter_group's 2 x 64 u16, for X and for Y (complex families)
-        if (complex_ops > 0) o += 512;
         total = (uint32_t)o;
     }
 };

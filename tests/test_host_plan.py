@@ -133,6 +133,29 @@ def test_family_size_limit(native):
             mat(plan_f(raw, "full", ref))
 
 
+@pytest.mark.parametrize("native", [True, False])
+def test_filter_slot_limit(native):
+    """k_large keeps each source read's simplified cigar at a 16-bit offset into the family's
+    slots -- one per M-only record, ops + 2 per complex record -- and packs the op count above it,
+    so the last record's offset must stay below 65536: a family holding a complex cigar may have
+    BSDC_MAX_FILTER_SLOTS = 65536 slots.  With 17-op forward records (19 slots) and plain reverse
+    ones (1), 3,276 templates need 65,520 and materialize; 3,277 need 65,540 and are refused by
+    name, in the C++ planner and in the numpy statement (k_small's 64 records cannot get there; a
+    family without a complex cigar runs no filter and is not bounded).  No kernel runs."""
+    import align_inputs as A
+    plan_f = hostplan.plan_families if native else batch.plan_families_py
+    mat = (lambda p: hostplan.materialize(p, 0, p.n_fam, 0)) if native else (lambda p: batch.materialize_py(p, 0, p.n_fam, 0))
+    assert batch.MAX_FILTER_SLOTS == 65536
+    c = A.slot_family(3276)
+    fb = mat(plan_f(c.raw, "vote", c.ref))
+    assert fb.n_fam == 1 and fb.n_rec == 2 * 3276
+    assert int(((fb.rec_link & batch.LINK_COMPLEX) != 0).sum()) == 3276
+    assert int((fb.cig_info[(fb.rec_link & batch.LINK_COMPLEX) != 0] & 0xFFFF).sum()) + 2 * 3276 + 3276 == 65520
+    c = A.slot_family(3277)
+    with pytest.raises(ValueError, match="65536 cigar slots"):
+        mat(plan_f(c.raw, "vote", c.ref))
+
+
 def test_empty_input():
     s = synth.generate("C0", 10, seed=1, device="cpu", genome_len=20_000)
     from bsseqconsensusreads_amd import records as R
