@@ -8,18 +8,26 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # BSDC_LIB_PATH: an alternative build of the same library (profiling A/B runs only)
 LIB_PATH = os.environ.get("BSDC_LIB_PATH") or os.path.join(HERE, "libbsdc.so")
 
-BSDC_ABI_VERSION = 15
+BSDC_ABI_VERSION = 16
 SMALL_BUCKETS = 8  # BSDC_SMALL_BUCKETS
 LARGE_BUCKETS = 6  # BSDC_LARGE_BUCKETS
 MODE_CONVERT, MODE_EXTEND, MODE_VOTE, MODE_DUMP = 1, 2, 4, 8
 MODE_SKIP_SMALL, MODE_SKIP_LARGE = 16, 32
 MODE_TAGS = 64  # single-strand reads + column statistics for the consensus tags
+FILT_MINREADS, FILT_READERR, FILT_NOCALL, FILT_MEANQ = 1, 2, 4, 8  # bsdc_filter's reason bits
 
 
 class Params(C.Structure):
     _fields_ = [("error_rate_pre_umi", C.c_double), ("error_rate_post_umi", C.c_double),
                 ("min_input_base_quality", C.c_int32), ("consensus_call_overlapping_bases", C.c_int32),
                 ("min_reads", C.c_int32), ("min_consensus_base_quality", C.c_int32)]
+
+
+class FilterParamsC(C.Structure):
+    _fields_ = [("min_reads", C.c_int32 * 3), ("max_read_error_rate", C.c_double * 3),
+                ("max_base_error_rate", C.c_double * 3), ("min_base_quality", C.c_int32),
+                ("max_no_call_fraction", C.c_double), ("min_mean_base_quality", C.c_int32),
+                ("require_single_strand_agreement", C.c_int32)]
 
 
 class FamilyBatchC(C.Structure):
@@ -48,7 +56,7 @@ EXPORTS = ("bsdc_abi_version", "bsdc_ctx_create", "bsdc_ctx_set_params", "bsdc_c
            "bsdc_load_reference", "bsdc_run", "bsdc_convert", "bsdc_extend", "bsdc_duplex_call",
            "bsdc_family_arena_bytes", "bsdc_small_arena_bytes", "bsdc_get_tables", "bsdc_model_tables",
            "bsdc_model_tables_fp64", "bsdc_agree_tables", "bsdc_phred_buckets", "bsdc_bgzf_scratch_bytes",
-           "bsdc_bgzf_deflate", "bsdc_bgzf_pack", "bsdc_host_register", "bsdc_host_unregister")
+           "bsdc_bgzf_deflate", "bsdc_bgzf_pack", "bsdc_host_register", "bsdc_host_unregister", "bsdc_filter")
 
 _lib = None
 
@@ -103,6 +111,9 @@ def load(path: str = LIB_PATH):
     lib.bsdc_host_unregister.restype = C.c_int32
     lib.bsdc_phred_buckets.argtypes = [C.c_double, C.c_double, C.c_void_p]
     lib.bsdc_phred_buckets.restype = None
+    lib.bsdc_filter.argtypes = [C.c_void_p, C.POINTER(FilterParamsC), C.c_int32, C.c_int64, C.POINTER(ConsensusC),
+                                C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bsdc_filter.restype = C.c_int32
     if lib.bsdc_abi_version() != BSDC_ABI_VERSION:
         raise RuntimeError("libbsdc ABI %d != %d" % (lib.bsdc_abi_version(), BSDC_ABI_VERSION))
     if path == LIB_PATH:

@@ -26,6 +26,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import filter as _filter
 from . import records as R
 
 IO_LIB_PATH = os.environ.get("BSDC_IO_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)),
@@ -1168,9 +1169,11 @@ def duplex_records(cons, raw: R.RawRecords, prefix: str, threads: int = 0, molec
     """fgbio duplex output records for the emitted families of `cons`
     (pipeline.Consensus, family order): R1 then R2 per family; fgbio's consensus tags appended
     when cons.ss holds the single-strand reads (``molecular``: CallMolecularConsensusReads' set).
-    `pool`: the tags' buffer comes from it (consensus_tags)."""
+    `pool`: the tags' buffer comes from it (consensus_tags).  A filtered consensus (cons.filt) gives
+    the kept families only, SEQ / QUAL masked; their tags are those of the unfiltered reads, as
+    fgbio FilterConsensusReads leaves them."""
     lib = _load()
-    em = np.nonzero((cons.status & 1) != 0)[0]
+    em = np.nonzero(_filter.kept(cons))[0]
     F = em.shape[0]
     n = 2 * F
     # consensus UMI per family from its records' RX (libbsdc_io)
@@ -1230,7 +1233,8 @@ def duplex_records(cons, raw: R.RawRecords, prefix: str, threads: int = 0, molec
         cigar=np.zeros(0, np.uint32), seq_off=seq_off, seq=seq, qual=qual, aux=auxs_t, aux2=tg)
 
 
-def consensus_sharded(eng, raw: R.RawRecords, tags: bool, batch_bases: Optional[int] = None, dist=None):
+def consensus_sharded(eng, raw: R.RawRecords, tags: bool, batch_bases: Optional[int] = None, dist=None,
+                      filter=None):
     """pipeline.run_step5 over the ranks of `dist` (None = this process alone): every rank forms
     the same family plan, runs the batches shard.deal gives it on its own GPU, and rank 0 gets the
     consensus of all batches in plan order (shard.gather_in_order; other ranks get None).  A plan
@@ -1238,7 +1242,9 @@ def consensus_sharded(eng, raw: R.RawRecords, tags: bool, batch_bases: Optional[
     two-launch fallback)."""
     from . import pipeline, shard
     if dist is None or dist.get_world_size() == 1:
-        return pipeline.run_step5(eng, raw, tags=tags, batch_bases=batch_bases)[0]
+        return pipeline.run_step5(eng, raw, tags=tags, batch_bases=batch_bases, filter=filter)[0]
+    if filter is not None:
+        raise ValueError("the consensus filter is not supported with several ranks yet")
     rank, world = dist.get_rank(), dist.get_world_size()
     plan = pipeline.plan_families(raw, "full", eng.ref)
     if plan.split_ext:
@@ -1253,12 +1259,14 @@ def consensus_sharded(eng, raw: R.RawRecords, tags: bool, batch_bases: Optional[
 
 def step5(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, prefix: Optional[str] = None, threads: int = 0,
           level: int = 6, fastq: Optional[Tuple[str, str]] = None, tags: bool = True, batch_bases: Optional[int] = None,
-          dist=None) -> dict:
+          dist=None, filter=None) -> dict:
     """Rules convert_Bstrain .. callduplex (main.snake.py:121-164) as one call on files; with
     `fastq`, also the following consensusduplex_to_fq rule (main.snake.py:167-177) straight from
     the consensus records (out_bam may then be None: no BAM round trip).  The stream runs as
     bounded device batches (batch_bases, pipeline.DEFAULT_BATCH_BASES); with `dist` the batches
-    are shared by the ranks (one GPU each) and rank 0 writes the files."""
+    are shared by the ranks (one GPU each) and rank 0 writes the files.  filter (filter.FilterParams):
+    fgbio FilterConsensusReads on the device between the vote and the records -- the outputs hold
+    the kept templates, masked, and the info dict a `filter` entry (filter.summary)."""
     from .device import Engine
     header, raw = read_bam(in_bam, threads)
     ref = read_fasta(fasta, header)
@@ -1266,7 +1274,7 @@ def step5(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, prefix: 
     eng = Engine(0) if own else engine
     try:
         eng.load_reference(ref)
-        cons = consensus_sharded(eng, raw, tags and out_bam is not None, batch_bases, dist)
+        cons = consensus_sharded(eng, raw, tags and out_bam is not None, batch_bases, dist, filter)
     finally:
         if own:
             eng.close()
@@ -1277,25 +1285,35 @@ def step5(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, prefix: 
         write_bam(out_bam, output_header(header), recs, level, threads)
     if fastq is not None:
         write_fastq(fastq[0], fastq[1], recs, level, threads)
-    return {"records_in": raw.n, "families": int(cons.status.shape[0]),
-            "families_emitted": int(((cons.status & 1) != 0).sum()), "records_out": recs.n}
+    return _with_filter({"records_in": raw.n, "families": int(cons.status.shape[0]),
+                         "families_emitted": int(((cons.status & 1) != 0).sum()), "records_out": recs.n}, cons, filter)
+
+
+def _with_filter(info: dict, cons, flt) -> dict:
+    """info plus the `filter` entry of a filtered consensus."""
+    if flt is not None:
+        info["filter"] = _filter.summary(cons)
+    return info
 
 
 def step5_stream(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, prefix: Optional[str] = None,
                  threads: int = 0, level: int = 6, fastq: Optional[Tuple[str, str]] = None, tags: bool = True,
                  chunk_bytes: int = DEFAULT_CHUNK_BYTES, slack: int = DEFAULT_SLACK,
                  batch_bases: Optional[int] = None, stats: Optional[dict] = None, gpu_bgzf: bool = False,
-                 defer: Optional[int] = None, read_size: int = 8 << 20) -> dict:
+                 defer: Optional[int] = None, read_size: int = 8 << 20, filter=None) -> dict:
     """step5 in bounded memory, pipelined (_stream_step); defer: the span past which a template is
-    deferred (default DEFAULT_DEFER_SPAN; 0 = off); read_size: compressed bytes per refill."""
+    deferred (default DEFAULT_DEFER_SPAN; 0 = off); read_size: compressed bytes per refill;
+    filter: as step5's."""
     return _public(_stream_step(in_bam, fasta, out_bam, engine, prefix, threads, level, fastq, tags, chunk_bytes,
-                                slack, batch_bases, stats, gpu_bgzf, None, defer=defer, read_size=read_size))
+                                slack, batch_bases, stats, gpu_bgzf, None, defer=defer, read_size=read_size,
+                                flt=filter))
 
 
 def molecular_stream(in_bam: str, out_bam: Optional[str], engine=None, prefix: Optional[str] = None, threads: int = 0,
                      level: int = 6, fastq: Optional[Tuple[str, str]] = None, tags: bool = True,
                      chunk_bytes: int = DEFAULT_CHUNK_BYTES, batch_bases: Optional[int] = None,
-                     stats: Optional[dict] = None, gpu_bgzf: bool = False, min_consensus_base_quality: int = 0) -> dict:
+                     stats: Optional[dict] = None, gpu_bgzf: bool = False, min_consensus_base_quality: int = 0,
+                     filter=None) -> dict:
     """Rule call_consensus_reads_molecular (main.snake.py:46-55) in bounded memory: the same
     pipeline as step5_stream over a GroupReadsByUmi-ordered input cut between MI runs
     (stream_chunks(runs=True)); each chunk's runs are its consensus families (pipeline.molecular_records,
@@ -1303,7 +1321,8 @@ def molecular_stream(in_bam: str, out_bam: Optional[str], engine=None, prefix: O
     molecular()'s whole-file path: no run straddles two chunks.  The reference's rule needs -Xmx100g
     (main.snake.py:54, README.md:83); this holds about six chunks."""
     return _public(_stream_step(in_bam, None, out_bam, engine, prefix, threads, level, fastq, tags, chunk_bytes,
-                                DEFAULT_SLACK, batch_bases, stats, gpu_bgzf, int(min_consensus_base_quality)))
+                                DEFAULT_SLACK, batch_bases, stats, gpu_bgzf, int(min_consensus_base_quality),
+                                flt=filter))
 
 
 def _public(info: dict) -> dict:
@@ -1330,7 +1349,7 @@ def _family_cuts(cons, raw, plan, splices, strict: bool, start: int = 0):
     first = plan.order[plan.fam_off[:-1]]
     k0, k1 = raw.tc_key[first, 0], raw.tc_key[first, 1]
     em = np.zeros(F + 1, np.int64)
-    em[1:] = np.cumsum((cons.status & 1) != 0)
+    em[1:] = np.cumsum(_filter.kept(cons))
     out, lo, j = [], 0, start
     while j < splices.shape[0]:
         s0, s1 = int(splices[j, 0]), int(splices[j, 1]) - (0 if strict else DEFER_MARGIN)
@@ -1355,7 +1374,7 @@ def _region_cuts(cons, raw, plan, prev: list) -> list:
     first = plan.order[plan.fam_off[:-1]]
     k0 = raw.tc_key[first, 0]
     em = np.zeros(k0.shape[0] + 1, np.int64)
-    em[1:] = np.cumsum((cons.status & 1) != 0)
+    em[1:] = np.cumsum(_filter.kept(cons))
     before = np.empty_like(k0)
     before[0] = k0[0] if prev[0] is None else prev[0]
     before[1:] = k0[:-1]
@@ -1428,7 +1447,7 @@ def _stream_step(in_bam: str, fasta: Optional[str], out_bam: Optional[str], engi
                  molecular: Optional[int], rng=None, fragment: Optional[str] = None, runner=None,
                  range_stats: Optional[dict] = None, owner=None, spill: Optional[str] = None,
                  marks: Optional[list] = None, defer: Optional[int] = None, late_splices=None,
-                 first_key=None, read_size: int = 8 << 20, regions: bool = False) -> dict:
+                 first_key=None, read_size: int = 8 << 20, regions: bool = False, flt=None) -> dict:
     """step5 (molecular None) or step 1 (molecular = its --min-consensus-base-quality) in bounded
     memory, pipelined: a decoder thread cuts the next chunk of the
     coordinate-sorted input (stream_bam: inflate, split where no template or MI family straddles),
@@ -1459,7 +1478,9 @@ def _stream_step(in_bam: str, fasta: Optional[str], out_bam: Optional[str], engi
     runs the second pass and the assembly; first_key = the sort key of the rank's first piece;
     regions (the ranks' passes) = also cut before the first family of every new key contig pair
     (a piece keyed (pair, MINKEY)): a rank does not register cross keys (bsdc_io.cpp), so the
-    deferred families of a contig's cross keys go between those pieces."""
+    deferred families of a contig's cross keys go between those pieces.
+    flt (filter.FilterParams): every batch is filtered on the device after its vote (step5's
+    `filter`); an Engine stream only."""
     import queue
     import threading
     import time
@@ -1474,13 +1495,15 @@ def _stream_step(in_bam: str, fasta: Optional[str], out_bam: Optional[str], engi
         eng = Engine(0) if own else engine
     else:
         eng = None
-        if gpu_bgzf or molecular is not None:
-            raise ValueError("a runner stream: step 5 with host deflate only")
+        if gpu_bgzf or molecular is not None or flt is not None:
+            raise ValueError("a runner stream: step 5 with host deflate only, unfiltered")
     chunks: "queue.Queue" = queue.Queue(maxsize=1)
     outs: "queue.Queue" = queue.Queue(maxsize=1)
     err: list = []
     info = {"records_in": 0, "families": 0, "families_emitted": 0, "records_out": 0, "chunks": 0,
             "spilled_bytes": 0, "deferred_families": 0, "splices": []}
+    if flt is not None:
+        info["filter"] = _filter.empty_summary()
     # deferral (step 5): the spill file and the output's pieces
     dspan = 0 if molecular is not None else (DEFAULT_DEFER_SPAN if defer is None else int(defer))
     late = None if late_splices is None else np.asarray(late_splices, np.int64).reshape(-1, 2)
@@ -1742,15 +1765,18 @@ def _stream_step(in_bam: str, fasta: Optional[str], out_bam: Optional[str], engi
                         cons = pipeline.concat_consensus(parts)
                         del fbs, parts
                 elif fbs is None:
-                    cons = pipeline.run_step5(eng, raw, tags=tg, batch_bases=batch_bases)[0]
+                    cons = pipeline.run_step5(eng, raw, tags=tg, batch_bases=batch_bases, filter=flt)[0]
                 else:
-                    cons = pipeline.concat_consensus(pipeline.run_batches(eng, fbs, mode, tg, G))
+                    fkw = {} if flt is None else {"filter": flt, "molecular": molecular is not None}
+                    cons = pipeline.concat_consensus(pipeline.run_batches(eng, fbs, mode, tg, G, **fkw))
                     del fbs
                 T["gpu"] += time.perf_counter() - t0
                 info["records_in"] += raw.n
                 info["families"] += int(cons.status.shape[0])
                 info["families_emitted"] += int(((cons.status & 1) != 0).sum())
                 info["chunks"] += 1
+                if flt is not None:
+                    info["filter"] = _filter.add_summary(info["filter"], _filter.summary(cons))
                 cuts = []
                 if late is not None:  # the spill's pass: cut before the families of each deferred key
                     cuts, lj[0] = _family_cuts(cons, raw, plan, late, False, lj[0])
@@ -1779,7 +1805,8 @@ def _stream_step(in_bam: str, fasta: Optional[str], out_bam: Optional[str], engi
                 if dspan else np.zeros((0, 2), np.int64)
             if solo and dspan:  # the deferred templates' pass and the assembly (or just the EOF blocks)
                 _finish_deferred(in_bam, fasta, out_bam, fastq, eng if runner is None else None, runner, first["prefix"],
-                                 threads, level, tags, chunk_bytes, slack, batch_bases, gpu_bgzf, mk, spill_path, info)
+                                 threads, level, tags, chunk_bytes, slack, batch_bases, gpu_bgzf, mk, spill_path, info,
+                                 flt)
     finally:
         flags.__exit__(None, None, None)
         if own:
@@ -1796,7 +1823,7 @@ def _stream_step(in_bam: str, fasta: Optional[str], out_bam: Optional[str], engi
 
 
 def _finish_deferred(in_bam, fasta, out_bam, fastq, eng, runner, prefix, threads, level, tags, chunk_bytes, slack,
-                     batch_bases, gpu_bgzf, marks, spill_path, info):
+                     batch_bases, gpu_bgzf, marks, spill_path, info, flt=None):
     """One process's deferred templates: with none, the EOF blocks the fragment-mode writers left
     out; else the spill's records as their own BAM through the stream (no deferral; cut at every
     deferred key), then the pieces of both outputs assembled in key order."""
@@ -1816,9 +1843,11 @@ def _finish_deferred(in_bam, fasta, out_bam, fastq, eng, runner, prefix, threads
         mk2: list = []
         inf2 = _stream_step(sb, fasta, p2[0], eng, prefix, threads, level, (p2[1], p2[2]) if fastq else None, tags,
                             chunk_bytes, slack, batch_bases, None, gpu_bgzf, None, fragment="next",
-                            runner=runner, marks=mk2, defer=0, late_splices=info["splices"])
+                            runner=runner, marks=mk2, defer=0, late_splices=info["splices"], flt=flt)
         for k in ("records_in", "families", "families_emitted", "records_out"):
             info[k] += inf2[k]
+        if flt is not None:
+            info["filter"] = _filter.add_summary(info["filter"], inf2["filter"])
         pieces = pieces_of(marks, paths, 0, 0) + pieces_of(mk2, p2, 1, 0)
         for k in range(3):
             if paths[k] is not None:
@@ -1831,9 +1860,10 @@ def _finish_deferred(in_bam, fasta, out_bam, fastq, eng, runner, prefix, threads
 
 def molecular(in_bam: str, out_bam: Optional[str], engine=None, prefix: Optional[str] = None, threads: int = 0,
               level: int = 6, fastq: Optional[Tuple[str, str]] = None, tags: bool = True,
-              min_consensus_base_quality: int = 0) -> dict:
+              min_consensus_base_quality: int = 0, filter=None) -> dict:
     """Rule call_consensus_reads_molecular (main.snake.py:46-55, fgbio CallMolecularConsensusReads)
-    on files; with `fastq`, also consensus_to_fq_unfiltered (main.snake.py:58-67)."""
+    on files; with `fastq`, also consensus_to_fq_unfiltered (main.snake.py:58-67) -- or, with
+    `filter` (as step5's, the molecular rules), the filtered pair of consensus_to_fq (:70-80)."""
     from . import pipeline
     from .device import Engine
     header, raw = read_bam(in_bam, threads)
@@ -1841,7 +1871,7 @@ def molecular(in_bam: str, out_bam: Optional[str], engine=None, prefix: Optional
     eng = Engine(0) if own else engine
     try:
         cons, rm = pipeline.run_molecular(eng, raw, tags=tags and out_bam is not None,
-                                          min_consensus_base_quality=min_consensus_base_quality)
+                                          min_consensus_base_quality=min_consensus_base_quality, filter=filter)
     finally:
         if own:
             eng.close()
@@ -1850,5 +1880,5 @@ def molecular(in_bam: str, out_bam: Optional[str], engine=None, prefix: Optional
         write_bam(out_bam, output_header(header), recs, level, threads)
     if fastq is not None:
         write_fastq(fastq[0], fastq[1], recs, level, threads)
-    return {"records_in": raw.n, "families": int(cons.status.shape[0]),
-            "families_emitted": int(((cons.status & 1) != 0).sum()), "records_out": recs.n}
+    return _with_filter({"records_in": raw.n, "families": int(cons.status.shape[0]),
+                         "families_emitted": int(((cons.status & 1) != 0).sum()), "records_out": recs.n}, cons, filter)

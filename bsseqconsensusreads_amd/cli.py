@@ -6,6 +6,11 @@
     python -m bsseqconsensusreads_amd.cli molecular IN.bam OUT.bam [--fastq1 F1 --fastq2 F2]
         rule call_consensus_reads_molecular (main.snake.py:46-55) [+ consensus_to_fq_unfiltered]
 
+Both take fgbio FilterConsensusReads' options as --filter-* (DESIGN.md 3.8): with
+--filter-min-base-quality the consensus is filtered on the GPU before any output is built, so
+OUT.bam and the FASTQ pair hold the kept, masked templates (rule consensus_to_fq's input,
+main.snake.py:70-80, with no FilterConsensusReads run; --gpus 1 only).
+
 OUT.bam may be '-' to skip the BAM when only the FASTQ pair is wanted.  Errors exit non-zero with
 the message on stderr, so Snakemake aborts the rule and removes partial outputs, as it does for
 the reference tools (tools/2.extend_gap.py:179-180 raises on a record without MI).
@@ -71,7 +76,30 @@ def parse(argv):
                                 "GroupReadsByUmi order of the input); false = read the whole BAM first")
         p.add_argument("--output-per-base-tags", default="true", choices=["true", "false"],
                        help="fgbio's consensus tags (per-read and per-base statistics); off = name/SEQ/QUAL/RG/MI/RX")
+        g = p.add_argument_group("consensus filter (fgbio FilterConsensusReads; off unless --filter-min-base-quality)")
+        g.add_argument("--filter-min-base-quality", type=int, default=None, metavar="Q",
+                       help="-N: mask consensus bases below Q to N; turns the filter on")
+        g.add_argument("--filter-min-reads", type=int, nargs="+", default=None, metavar="M",
+                       help="-M: one to three values, duplex / AB / BA (default 1)")
+        g.add_argument("--filter-max-read-error-rate", type=float, nargs="+", default=None, metavar="E",
+                       help="-E: one to three values (default 0.025)")
+        g.add_argument("--filter-max-base-error-rate", type=float, nargs="+", default=None, metavar="E",
+                       help="-e: one to three values (default 0.1)")
+        g.add_argument("--filter-max-no-call-fraction", type=float, default=None, metavar="F", help="-n (default 0.2)")
+        g.add_argument("--filter-min-mean-base-quality", type=int, default=None, metavar="Q", help="-q (default: off)")
+        g.add_argument("--filter-require-single-strand-agreement", default=None, choices=("true", "false"),
+                       help="-s: mask duplex bases whose two single-strand calls differ (default false)")
     a = ap.parse_args(argv)
+    others = [k for k in ("min_reads", "max_read_error_rate", "max_base_error_rate", "max_no_call_fraction",
+                          "min_mean_base_quality", "require_single_strand_agreement")
+              if getattr(a, "filter_" + k) is not None]
+    if a.filter_min_base_quality is None and others:
+        ap.error("--filter-%s needs --filter-min-base-quality (which turns the filter on)" % others[0].replace("_", "-"))
+    for k in ("min_reads", "max_read_error_rate", "max_base_error_rate"):
+        if getattr(a, "filter_" + k) is not None and len(getattr(a, "filter_" + k)) > 3:
+            ap.error("--filter-%s takes one to three values" % k.replace("_", "-"))
+    if a.filter_min_base_quality is not None and getattr(a, "gpus", 1) > 1:
+        ap.error("the consensus filter is not supported with --gpus %d yet" % a.gpus)
     if (a.fastq1 is None) != (a.fastq2 is None):
         ap.error("--fastq1 and --fastq2 go together")
     if a.output == "-" and a.fastq1 is None:
@@ -80,6 +108,18 @@ def parse(argv):
         print("warning: --gpu-bgzf applies to the streaming step only; --stream false deflates on the host",
               file=sys.stderr)
     return a
+
+
+def filter_params(a):
+    """The --filter-* options as filter.FilterParams, None when the filter is off."""
+    if a.filter_min_base_quality is None:
+        return None
+    from .filter import FilterParams
+    kw = {k: getattr(a, "filter_" + k) for k in ("max_no_call_fraction", "min_mean_base_quality")}
+    kw.update({k: tuple(getattr(a, "filter_" + k)) for k in ("min_reads", "max_read_error_rate", "max_base_error_rate")
+               if getattr(a, "filter_" + k) is not None})
+    kw["require_single_strand_agreement"] = a.filter_require_single_strand_agreement == "true"
+    return FilterParams(a.filter_min_base_quality, **{k: v for k, v in kw.items() if v is not None})
 
 
 def _coordinate_sorted(bam, path: str) -> bool:
@@ -149,6 +189,7 @@ def main(argv=None) -> int:
     from .device import Engine
     out = None if a.output == "-" else a.output
     fq = (a.fastq1, a.fastq2) if a.fastq1 else None
+    flt = filter_params(a)
     dist = None
     try:
         dist = shard.init("gloo") if world > 1 else None  # host gather of the batch outputs only
@@ -159,19 +200,20 @@ def main(argv=None) -> int:
             if stream:
                 info = bam.step5_stream(a.input, a.reference, out, eng, a.read_name_prefix, a.threads, a.compression,
                                         fq, tags=a.output_per_base_tags == "true", chunk_bytes=a.chunk_mb << 20,
-                                        batch_bases=a.batch_bases, gpu_bgzf=a.gpu_bgzf == "true")
+                                        batch_bases=a.batch_bases, gpu_bgzf=a.gpu_bgzf == "true", filter=flt)
             elif a.cmd == "step5":
                 info = bam.step5(a.input, a.reference, out, eng, a.read_name_prefix, a.threads, a.compression, fq,
-                                 tags=a.output_per_base_tags == "true", batch_bases=a.batch_bases, dist=dist)
+                                 tags=a.output_per_base_tags == "true", batch_bases=a.batch_bases, dist=dist,
+                                 filter=flt)
             elif a.stream == "true":
                 info = bam.molecular_stream(a.input, out, eng, a.read_name_prefix, a.threads, a.compression, fq,
                                             tags=a.output_per_base_tags == "true", chunk_bytes=a.chunk_mb << 20,
                                             batch_bases=a.batch_bases, gpu_bgzf=a.gpu_bgzf == "true",
-                                            min_consensus_base_quality=a.min_consensus_base_quality)
+                                            min_consensus_base_quality=a.min_consensus_base_quality, filter=flt)
             else:
                 info = bam.molecular(a.input, out, eng, a.read_name_prefix, a.threads, a.compression, fq,
                                      tags=a.output_per_base_tags == "true",
-                                     min_consensus_base_quality=a.min_consensus_base_quality)
+                                     min_consensus_base_quality=a.min_consensus_base_quality, filter=flt)
         finally:
             eng.close()
     except Exception as e:  # noqa: BLE001 -- the rule fails with the message, like the tools do

@@ -2921,6 +2921,16 @@ struct bsdc_ctx {
     hipEvent_t ev_fork = nullptr, ev_join[kForkStreams] = {};
 };
 
+// what csrc/bsdc_filter.hip needs of a context (the struct stays private to this file): its
+// device, and its error text set
+namespace bsdc_internal {
+int ctx_device(const bsdc_ctx *c) { return c->device; }
+int32_t ctx_fail(bsdc_ctx *c, int32_t code, const std::string &msg) {
+    c->err = msg;
+    return code;
+}
+}  // namespace bsdc_internal
+
 static int phred_agree(int64_t D, const float *thr) {
     const float x = (float)((double)(-D) * 9.5367431640625e-07);
     const float e = x < -80.0f ? 0.0f : det_expf(x);

@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from .batch import FamilyBatch, wide_rows
+from .filter import FilterParams
 from .records import Reference
 
 
@@ -54,7 +55,8 @@ def _dptr(t: torch.Tensor) -> int:
 class DeviceBatch:
     """A FamilyBatch resident in HBM plus its output buffers."""
 
-    def __init__(self, fb: FamilyBatch, device: torch.device, dump: bool = False, tags: bool = False):
+    def __init__(self, fb: FamilyBatch, device: torch.device, dump: bool = False, tags: bool = False,
+                 filt: bool = False):
         self.fb = fb
         self.n_fam, self.n_rec = fb.n_fam, fb.n_rec
         self.device = device
@@ -97,6 +99,10 @@ class DeviceBatch:
                 self.t["ss_wide"] = torch.from_numpy(self.ss_wide.view(np.uint8)).to(device)
                 self.ss_wdepth = torch.zeros(nw, dtype=torch.int16, device=device)
                 self.ss_werr = torch.zeros(nw, dtype=torch.int16, device=device)
+        self.filt = self.masked = None
+        if filt:  # bsdc_filter's outputs: reason bits per family, newly masked columns per end
+            self.filt = torch.zeros(max(F, 1), dtype=torch.uint8, device=device)
+            self.masked = torch.zeros(max(2 * F, 1), dtype=torch.int16, device=device)
         # HBM scratch: arenas of the large buckets beyond the LDS budget, one region per bucket (the
         # bucket dispatches run concurrently on the library's side streams), the split families'
         # fallback arenas and their parts' sums (FamilyBatch.scratch_layout; + slack: dword reads
@@ -144,8 +150,10 @@ class DeviceBatch:
         return (self.status[:F].cpu().numpy(),
                 self.len[:2 * F].cpu().numpy().view(np.uint16).astype(np.int32).reshape(F, 2))
 
-    def fetch(self, alloc=None):
-        """-> dict of numpy arrays (consensus and, if dumped, the post-tool records).  The copies
+    def fetch(self, alloc=None, ss: bool = True):
+        """-> dict of numpy arrays (consensus and, if dumped, the post-tool records; after
+        Engine.filter also "filt" [F] and "masked" [F, 2]).  ss=False leaves the single-strand rows
+        of a tags batch in HBM (a filtered output without consensus tags).  The copies
         are queued together on the current stream into pinned host memory (torch's caching host
         allocator), then one synchronize.  With alloc(nbytes) -> uint8 array (a fleet worker's
         shared segment) the outputs land in that buffer instead, so they leave the worker by name."""
@@ -153,7 +161,10 @@ class DeviceBatch:
         t = {"status": self.status[:F], "len": self.len[:2 * F], "seq": self.seq[:F * self.stride],
              "qual": self.qual[:2 * F * self.stride]}
         n = 4 * F * self.stride
-        if self.tags:
+        ss = ss and self.tags
+        if self.filt is not None:
+            t.update(filt=self.filt[:F], masked=self.masked[:2 * F])
+        if ss:
             t.update(ss_len=self.ss_len[:4 * F], ss_base=self.ss_base[:n], ss_qual=self.ss_qual[:n],
                      ss_depth=self.ss_depth[:n], ss_err=self.ss_err[:n])
             if self.n_wide:
@@ -184,7 +195,10 @@ class DeviceBatch:
             "qual": a["qual"].reshape(F, 2, self.stride),
             "stride": self.stride,
         }
-        if self.tags:
+        if self.filt is not None:
+            out["filt"] = a["filt"]
+            out["masked"] = a["masked"].view(np.uint16).astype(np.int32).reshape(F, 2)
+        if ss:
             out["ss_len"] = a["ss_len"].view(np.uint16).astype(np.int32).reshape(F, 4)
             out["ss_base"] = a["ss_base"].reshape(F, 4, self.stride)
             out["ss_qual"] = a["ss_qual"].reshape(F, 4, self.stride)
@@ -320,14 +334,28 @@ class Engine:
         self._check(rc, "bsdc_load_reference")
         self.ref = ref
 
-    def upload(self, fb: FamilyBatch, dump: bool = False, tags: bool = False) -> DeviceBatch:
+    def upload(self, fb: FamilyBatch, dump: bool = False, tags: bool = False, filt: bool = False) -> DeviceBatch:
+        """filt: also the outputs of `filter` (which reads the tags' rows: tags is then on)."""
         with torch.cuda.device(self.device):
-            return DeviceBatch(fb, self.device, dump, tags)
+            return DeviceBatch(fb, self.device, dump, tags or filt, filt)
 
     def run(self, db: DeviceBatch, mode: int, stream: Optional[torch.cuda.Stream] = None):
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
         rc = self.lib.bsdc_run(self.ctx, C.byref(db._b), C.byref(db._o), mode, C.c_void_p(s.cuda_stream))
         self._check(rc, "bsdc_run")
+
+    def filter(self, db: DeviceBatch, fparams: FilterParams, molecular: bool = False,
+               stream: Optional[torch.cuda.Stream] = None):
+        """fgbio FilterConsensusReads over a batch run with MODE_TAGS (bsdc_filter),
+        enqueued on the stream that ran it: db.seq / db.qual are masked in place, db.filt and
+        db.masked filled (fetch returns them).  molecular: step-1 records (one strand per end)."""
+        if db.filt is None:
+            raise ValueError("the batch was uploaded without filt=True")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        p = fparams.c_struct()
+        rc = self.lib.bsdc_filter(self.ctx, C.byref(p), 1 if molecular else 0, db.n_fam, C.byref(db._o),
+                                  C.c_void_p(_dptr(db.filt)), C.c_void_p(_dptr(db.masked)), C.c_void_p(s.cuda_stream))
+        self._check(rc, "bsdc_filter")
 
     def tables(self):
         lr = np.zeros(256, np.int64)

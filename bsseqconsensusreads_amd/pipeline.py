@@ -28,6 +28,8 @@ from . import shard
 from .batch import FamilyBatch, FamilyPlan, build_family_batch, materialize, plan_families
 from ._lib import MODE_CONVERT, MODE_DUMP, MODE_EXTEND, MODE_TAGS, MODE_VOTE
 
+from .filter import FilterParams
+
 if TYPE_CHECKING:  # (torch loads with the engine, not with the host planning: ranks.py overlaps the two)
     from .device import Engine
 
@@ -74,6 +76,12 @@ class Consensus:
     # exact u16 rows of the families of more than 255 records in "wdepth" / "werr" [W, 4, stride],
     # row "wide"[f], -1 none; batch.ss_stats16 merges them)
     ss: Optional[dict] = None
+    # with filter=FilterParams(...) (fgbio FilterConsensusReads on the device): filt
+    # u8 [F], 0 = kept or not emitted, else the reason bits (_lib.FILT_*) of the family's two
+    # ends; masked [F, 2] the columns newly masked to (N, 2), already applied to seq / qual.  The
+    # pairs that go out are those with status & 1 and filt == 0 (filter.kept)
+    filt: Optional[np.ndarray] = None
+    masked: Optional[np.ndarray] = None
 
 
 def _stripped_cigar(raw: R.RawRecords, k: int, strip: bool) -> List[int]:
@@ -231,7 +239,7 @@ def consensus_from_output(fb: FamilyBatch, out: dict) -> Consensus:
         ss = {"len": out["ss_len"], "base": out["ss_base"], "qual": out["ss_qual"], "depth": out["ss_depth"],
               "err": out["ss_err"], "wide": out["ss_wide"], "wdepth": out["ss_wdepth"], "werr": out["ss_werr"]}
     return Consensus(fb.fam_mi.copy(), out["status"], out["len"], seq, out["qual"], fb.fam_off.astype(np.int64),
-                     fb.src.astype(np.int64), ss)
+                     fb.src.astype(np.int64), ss, out.get("filt"), out.get("masked"))
 
 
 # Device batch budget: bases (+2 per record, the tools' prepend / append room) per launch.  2^31
@@ -246,10 +254,13 @@ def plan_ranges(plan: FamilyPlan, batch_bases: Optional[int] = None):
 
 
 def run_ranges(engine: Engine, plan: FamilyPlan, ranges, mode: int, tags: bool = False,
-               timing: Optional[dict] = None) -> List[Consensus]:
+               timing: Optional[dict] = None, filter: Optional[FilterParams] = None,
+               molecular: bool = False) -> List[Consensus]:
     """Plan family ranges through the kernels, one launch each, output per range in range order.
     The host builds range i + 1 while the kernels of range i run.  `timing`: seconds added per
-    host step (materialize, upload, fetch = wait + copy out, unpack)."""
+    host step (materialize, upload, fetch = wait + copy out, unpack).  `filter`: each range is
+    filtered on the device after its vote (Engine.filter; `molecular`: step-1 records), which
+    needs the tags' rows there; they are copied out only with `tags`."""
     import time
     T = timing if timing is not None else {}
     parts: List[Consensus] = []
@@ -257,7 +268,7 @@ def run_ranges(engine: Engine, plan: FamilyPlan, ranges, mode: int, tags: bool =
 
     def out(fb, db):
         t0 = time.perf_counter()
-        o = db.fetch()
+        o = db.fetch(ss=tags)
         t1 = time.perf_counter()
         parts.append(consensus_from_output(fb, o))
         T["fetch"] = T.get("fetch", 0.0) + t1 - t0
@@ -266,8 +277,10 @@ def run_ranges(engine: Engine, plan: FamilyPlan, ranges, mode: int, tags: bool =
         t0 = time.perf_counter()
         fb = materialize(plan, a, b, images=engine.stage_images)
         t1 = time.perf_counter()
-        db = engine.upload(fb, tags=tags)
-        engine.run(db, mode | (MODE_TAGS if tags else 0))
+        db = engine.upload(fb, tags=tags, filt=filter is not None)
+        engine.run(db, mode | (MODE_TAGS if db.tags else 0))
+        if filter is not None:
+            engine.filter(db, filter, molecular)
         T["materialize"] = T.get("materialize", 0.0) + t1 - t0
         T["upload"] = T.get("upload", 0.0) + time.perf_counter() - t1
         if prev is not None:
@@ -285,9 +298,11 @@ def materialize_ranges(plan: FamilyPlan, ranges, images=None) -> List[FamilyBatc
 
 
 def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
-                timing: Optional[dict] = None) -> List[Consensus]:
+                timing: Optional[dict] = None, filter: Optional[FilterParams] = None,
+                molecular: bool = False) -> List[Consensus]:
     """Materialized batches through the kernels, one launch each, output per batch in order; a
-    batch uploads and launches before the one before it is fetched.  `timing` as run_ranges."""
+    batch uploads and launches before the one before it is fetched.  `timing`, `filter` and
+    `molecular` as run_ranges."""
     import time
     T = timing if timing is not None else {}
     parts: List[Consensus] = []
@@ -295,15 +310,17 @@ def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
 
     def out(fb, db):
         t0 = time.perf_counter()
-        o = db.fetch()
+        o = db.fetch(ss=tags)
         t1 = time.perf_counter()
         parts.append(consensus_from_output(fb, o))
         T["fetch"] = T.get("fetch", 0.0) + t1 - t0
         T["unpack"] = T.get("unpack", 0.0) + time.perf_counter() - t1
     for fb in batches:
         t0 = time.perf_counter()
-        db = engine.upload(fb, tags=tags)
-        engine.run(db, mode | (MODE_TAGS if tags else 0))
+        db = engine.upload(fb, tags=tags, filt=filter is not None)
+        engine.run(db, mode | (MODE_TAGS if db.tags else 0))
+        if filter is not None:
+            engine.filter(db, filter, molecular)
         T["upload"] = T.get("upload", 0.0) + time.perf_counter() - t0
         if prev is not None:
             out(*prev)
@@ -346,10 +363,13 @@ def concat_consensus(parts: List[Consensus]) -> Consensus:
             ss["wide"] = np.concatenate(wides)
             for k in ("wdepth", "werr"):
                 ss[k] = np.concatenate([pad(p.ss[k]) for p in parts if p.ss.get(k) is not None])
+    filt = masked = None
+    if all(p.filt is not None for p in parts):
+        filt, masked = np.concatenate([p.filt for p in parts]), np.concatenate([p.masked for p in parts])
     return Consensus(np.concatenate([p.fam_mi for p in parts]), np.concatenate([p.status for p in parts]),
                      np.concatenate([p.length for p in parts]), np.concatenate([pad(p.seq) for p in parts]),
                      np.concatenate([pad(p.qual) for p in parts]), fro.astype(np.int64),
-                     np.concatenate([np.asarray(p.fam_src, np.int64) for p in parts]), ss)
+                     np.concatenate([np.asarray(p.fam_src, np.int64) for p in parts]), ss, filt, masked)
 
 
 def _tools_batched(engine: Engine, raw: R.RawRecords, batch_bases: Optional[int]) -> OutRecords:
@@ -386,33 +406,37 @@ def _cat_records(parts: List[OutRecords]) -> OutRecords:
 
 
 def run_step5(engine: Engine, raw: R.RawRecords, dump: bool = False, tags: bool = False,
-              batch_bases: Optional[int] = None):
+              batch_bases: Optional[int] = None, filter: Optional[FilterParams] = None):
     """Rules convert_Bstrain .. callduplex (main.snake.py:121-164) -> (Consensus, tool-2 records or None).
     tags: also the single-strand reads and column statistics of fgbio's consensus tags (Consensus.ss).
     batch_bases: device batch budget (DEFAULT_BATCH_BASES); dump (the tool-2 records, parity
-    tests) needs the stream in one batch."""
+    tests) needs the stream in one batch.  filter: fgbio FilterConsensusReads on the device after
+    the vote (Consensus.filt / masked; seq and qual come back masked)."""
     plan = plan_families(raw, "full", engine.ref)
     if plan.split_ext:
         # a TemplateCoordinate family lacks a record's tool-2 extension partner: run the tools as
         # their own launches (tool-2 MI groups), then callduplex on their records
         t2 = _tools_batched(engine, raw, batch_bases)
-        cons = run_duplex(engine, raw_from_records(raw, t2), tags, batch_bases)
+        cons = run_duplex(engine, raw_from_records(raw, t2), tags, batch_bases, filter)
         cons.fam_src = t2.src[cons.fam_src]  # raw2 record k is tool-2 record k
         return cons, (t2 if dump else None)
     mode = MODE_CONVERT | MODE_EXTEND | MODE_VOTE
     if dump:
         fb = materialize(plan, 0, plan.n_fam)
-        db = engine.upload(fb, dump=True, tags=tags)
-        engine.run(db, mode | MODE_DUMP | (MODE_TAGS if tags else 0))
-        out = db.fetch()
+        db = engine.upload(fb, dump=True, tags=tags, filt=filter is not None)
+        engine.run(db, mode | MODE_DUMP | (MODE_TAGS if db.tags else 0))
+        if filter is not None:
+            engine.filter(db, filter)
+        out = db.fetch(ss=tags)
         return consensus_from_output(fb, out), _records_from_dump(raw, fb, out, strip=True)
-    return concat_consensus(run_ranges(engine, plan, plan_ranges(plan, batch_bases), mode, tags)), None
+    return concat_consensus(run_ranges(engine, plan, plan_ranges(plan, batch_bases), mode, tags, filter=filter)), None
 
 
-def run_duplex(engine: Engine, raw: R.RawRecords, tags: bool = False, batch_bases: Optional[int] = None) -> Consensus:
+def run_duplex(engine: Engine, raw: R.RawRecords, tags: bool = False, batch_bases: Optional[int] = None,
+               filter: Optional[FilterParams] = None) -> Consensus:
     """callduplex alone (main.snake.py:155-164) on converted + extended records."""
     plan = plan_families(raw, "vote")
-    return concat_consensus(run_ranges(engine, plan, plan_ranges(plan, batch_bases), MODE_VOTE, tags))
+    return concat_consensus(run_ranges(engine, plan, plan_ranges(plan, batch_bases), MODE_VOTE, tags, filter=filter))
 
 
 def molecular_records(raw: R.RawRecords) -> R.RawRecords:
@@ -468,12 +492,14 @@ def _run_names(tab, ids: np.ndarray, strands: np.ndarray):
 
 
 def run_molecular(engine: Engine, raw: R.RawRecords, tags: bool = False,
-                  min_consensus_base_quality: int = 0):
+                  min_consensus_base_quality: int = 0, filter: Optional[FilterParams] = None):
     """fgbio CallMolecularConsensusReads with the step-1 flags (main.snake.py:54: pre 45, post 30,
     min-reads 1, min-consensus-base-quality 0, overlapping bases on) -> (Consensus over the runs,
     the run records).  Consensus family f is MI run f; its R1 / R2 are the single-strand consensus
-    of the run's R1s / R2s.  The engine runs with min_consensus_base_quality for this call only."""
+    of the run's R1s / R2s.  The engine runs with min_consensus_base_quality for this call only.
+    filter: as run_step5's, with the molecular rules."""
     rm = molecular_records(raw)
     plan = plan_families(rm, "vote", family_order="mi-group")
     with engine.flags(min_consensus_base_quality=min_consensus_base_quality):
-        return concat_consensus(run_ranges(engine, plan, plan_ranges(plan), MODE_VOTE, tags)), rm
+        return concat_consensus(run_ranges(engine, plan, plan_ranges(plan), MODE_VOTE, tags, filter=filter,
+                                           molecular=True)), rm

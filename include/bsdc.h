@@ -10,6 +10,8 @@
  *   bsdc_extend       replaces tools/2.extend_gap.py:112-140       (4-record gap extension)
  *   bsdc_duplex_call  replaces main.snake.py:155-164 fgbio CallDuplexConsensusReads (and, with
  *                     BSDC_MODE_CONVERT|BSDC_MODE_EXTEND in `mode`, the two tools in front of it)
+ *   bsdc_filter       replaces fgbio FilterConsensusReads, which the user runs on the unfiltered
+ *                     consensus before main.snake.py:70-80 (consensus_to_fq) can read its input
  *
  * Conventions: every function returns 0 on success and a negative errno-style code on failure
  * (message via bsdc_last_error).  Batch and output pointers are DEVICE pointers owned by the
@@ -26,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BSDC_ABI_VERSION 15
+#define BSDC_ABI_VERSION 16
 #define BSDC_SMALL_BUCKETS 8
 #define BSDC_LARGE_BUCKETS 6
 #define BSDC_LARGE_LDS_MAX 158912 /* LDS arena bytes one large-family workgroup may use */ /* LDS arena size classes of the wavefront-per-family kernel */
@@ -256,6 +258,38 @@ int32_t bsdc_bgzf_deflate(const uint8_t *in, int64_t n, int64_t blk0, int64_t nb
                           int32_t *sizes, void *stream);
 int32_t bsdc_bgzf_pack(const uint8_t *scratch, const int32_t *sizes, int64_t blk0, int64_t nblk, uint8_t *out,
                        void *stream);
+
+/* fgbio FilterConsensusReads on the device (the step every user of the unfiltered consensus runs
+ * next: the reference's consensus_to_fq rule, main.snake.py:70-80, reads a _molecular_filtered.bam),
+ * from the single-strand rows a BSDC_MODE_TAGS run left in HBM; rules in DESIGN.md section 3.8
+ * (restated from fgbio: PARITY UNPINNED).  The three-entry fields are ordered duplex ("cc"), AB,
+ * BA, as fgbio's one-to-three-valued flags.
+ * Supported domain (BSDC_EINVAL outside it, the message names the field): min_reads >= 0 and
+ * non-increasing; every rate and max_no_call_fraction in [0, 1]; min_base_quality 0..93;
+ * min_mean_base_quality -1..93. */
+typedef struct {
+    int32_t min_reads[3];               /* -M */
+    double max_read_error_rate[3];      /* -E (fgbio's default 0.025) */
+    double max_base_error_rate[3];      /* -e (0.1) */
+    int32_t min_base_quality;           /* -N: consensus bases below it become (N, 2) */
+    double max_no_call_fraction;        /* -n (0.2) */
+    int32_t min_mean_base_quality;      /* -q; -1 = off */
+    int32_t require_single_strand_agreement; /* -s */
+} bsdc_filter_params;
+
+#define BSDC_FILT_MINREADS 1  /* bsdc_filter's reason bits */
+#define BSDC_FILT_READERR 2
+#define BSDC_FILT_NOCALL 4
+#define BSDC_FILT_MEANQ 8
+
+/* Enqueued on the stream of the bsdc_run(.. | BSDC_MODE_TAGS) that filled `out`, after it.  kind: 0
+ * duplex (step 5), 1 molecular (step 1: rows 0 / 1 are R1 / R2, no BA side).  filt[f] = 0 for a
+ * family kept or not emitted, else the OR of the reason bits of its two ends; masked[2f + e] = the
+ * columns of end e newly masked to (N, 2); out->seq and out->qual are rewritten in place (an end
+ * that passed the read-level gate is masked even if the other end drops the template).  out->status
+ * and the ss_* rows are only read.  Device pointers; BSDC_EINVAL when out->ss_* are NULL. */
+int32_t bsdc_filter(bsdc_ctx *ctx, const bsdc_filter_params *params, int32_t kind, int64_t n_fam,
+                    bsdc_consensus *out, uint8_t *filt, uint16_t *masked, void *stream);
 
 #ifdef __cplusplus
 }
