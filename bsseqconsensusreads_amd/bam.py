@@ -22,7 +22,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 
@@ -261,9 +261,9 @@ class BufferPool:
 
 
 def _decode(lib, h, what: str, pool: Optional[BufferPool] = None):
-    """A bsdc_bam handle (whole file or stream chunk) -> (BamHeader, RawRecords); frees nothing.
-    With `pool`, the record arrays are carved from one pooled buffer (bsdc_bam_copy writes every
-    element), kept as RawRecords._pool_buf for the caller to give back."""
+    """A bsdc_bam handle (whole file or stream chunk) -> (BamHeader, RawRecords, pooled buffer);
+    frees nothing.  With `pool`, the record arrays are carved from one pooled buffer (bsdc_bam_copy
+    writes every element), returned for the caller to give back (else None)."""
     s = _Sizes()
     lib.bsdc_bam_sizes_of(h, C.byref(s))
     n = s.n_rec
@@ -309,8 +309,7 @@ def _decode(lib, h, what: str, pool: Optional[BufferPool] = None):
         mi_names=StringTable(A["mi_buf"][:s.mi_bytes], A["mi_off"][:s.n_mi + 1], as_str=True),
         mc_off=A["mc_off"][:n], mc_n=A["mc_n"][:n], mc_cigar=A["mc_cigar"][:s.n_mc],
         aux=StringTable(A["aux"][:s.aux_bytes], A["aux_off"][:n + 1]), la_tag=A["la"][:n], rd_tag=A["rd"][:n])
-    raw._pool_buf = buf
-    return header, raw
+    return header, raw, buf
 
 
 def read_bam(path: str, threads: int = 0):
@@ -322,7 +321,7 @@ def read_bam(path: str, threads: int = 0):
     if rc != 0:
         raise OSError("%s: %s" % (path, lib.bsdc_io_last_error().decode()))
     try:
-        return _decode(lib, h, path)
+        return _decode(lib, h, path)[:2]
     finally:
         lib.bsdc_bam_free(h)
 
@@ -363,6 +362,7 @@ class StreamChunk:
         self.keys = False      # decode() also fills RawRecords.tc_key (bsdc_bam_rec_keys)
         self.splices = None    # int64 [k, 2]: deferred keys to cut this chunk's output before
         self.spill = b""       # spill entries (bsdc_bam_stream_spill) since the chunk before
+        self.pool_buf = None   # decode(pool=...): the pooled buffer of the records, to give back
 
     def decode(self, threads: int = 0, timing: Optional[dict] = None, pool: Optional[BufferPool] = None):
         """-> (BamHeader, RawRecords); `timing`: seconds added under "parse" (records, tags,
@@ -375,7 +375,7 @@ class StreamChunk:
             if lib.bsdc_bam_parse(h, int(threads)) != 0:
                 raise OSError("%s: %s" % (self._path, lib.bsdc_io_last_error().decode()))
             t1 = time.perf_counter()
-            out = _decode(lib, h, self._path, pool)
+            *out, self.pool_buf = _decode(lib, h, self._path, pool)
             if self.keys:  # the records' coarse TemplateCoordinate keys (splicing deferred families)
                 kk = np.zeros(2 * max(out[1].n, 1), np.int64)
                 if lib.bsdc_bam_rec_keys(h, _ptr(kk)) != 0:
@@ -384,7 +384,7 @@ class StreamChunk:
             if timing is not None:
                 timing["parse"] = timing.get("parse", 0.0) + t1 - t0
                 timing["copy"] = timing.get("copy", 0.0) + time.perf_counter() - t1
-            return out
+            return tuple(out)
         finally:
             lib.bsdc_bam_stream_recycle(self._st, h)
 
@@ -1116,8 +1116,8 @@ def consensus_tags(cons, em: np.ndarray, molecular: bool = False, threads: int =
     single-strand reads in cons.ss (libbsdc_io bsdc_consensus_tags).  Duplex: a record's 'a'
     strand is its AB read (AB-R1 for R1, AB-R2 for R2), or the only strand present; 'b' its BA read
     when both are present.  Molecular: set 0 for R1, set 1 for R2.  With `pool`, the bytes land in
-    a pooled buffer (kept as the table's _pool_buf for the caller to give back): the tags are
-    ≈1.8 KB a record, and fresh pages for them cost as much as writing them."""
+    a pooled buffer and the result is (table, that buffer, for the caller to give back): the tags
+    are ≈1.8 KB a record, and fresh pages for them cost as much as writing them."""
     lib = _load()
     ss = cons.ss
     F = em.shape[0]
@@ -1160,8 +1160,7 @@ def consensus_tags(cons, em: np.ndarray, molecular: bool = False, threads: int =
     buf = pool.take(max(int(total), 1)) if pool is not None else np.empty(max(int(total), 1), np.uint8)
     lib.bsdc_consensus_tags(*args, _ptr(buf), int(threads))
     tab = StringTable(buf[:int(total)], off)
-    tab._pool_buf = buf if pool is not None else None
-    return tab
+    return tab if pool is None else (tab, buf)
 
 
 def duplex_records(cons, raw: R.RawRecords, prefix: str, threads: int = 0, molecular: bool = False,
@@ -1169,7 +1168,8 @@ def duplex_records(cons, raw: R.RawRecords, prefix: str, threads: int = 0, molec
     """fgbio duplex output records for the emitted families of `cons`
     (pipeline.Consensus, family order): R1 then R2 per family; fgbio's consensus tags appended
     when cons.ss holds the single-strand reads (``molecular``: CallMolecularConsensusReads' set).
-    `pool`: the tags' buffer comes from it (consensus_tags).  A filtered consensus (cons.filt) gives
+    `pool`: the tags' buffer comes from it (consensus_tags) and the result is (records, that buffer
+    or None, for the caller to give back).  A filtered consensus (cons.filt) gives
     the kept families only, SEQ / QUAL masked; their tags are those of the unfiltered reads, as
     fgbio FilterConsensusReads leaves them."""
     lib = _load()
@@ -1213,7 +1213,11 @@ def duplex_records(cons, raw: R.RawRecords, prefix: str, threads: int = 0, molec
     fam_names = _concat_fields([prefix.encode() + b":", mi], F)
     two = np.repeat(np.arange(F, dtype=np.int64), 2)
     names_t, auxs_t = _take_table(fam_names, two), _take_table(fam_aux, two)
-    tg = consensus_tags(cons, em, molecular, threads, pool) if getattr(cons, "ss", None) is not None else None
+    tg = tags_buf = None
+    if getattr(cons, "ss", None) is not None:
+        tg = consensus_tags(cons, em, molecular, threads, pool)
+        if pool is not None:
+            tg, tags_buf = tg
     L = np.ascontiguousarray(cons.length[em].reshape(-1), np.int32)  # R1, R2, R1, R2 ...
     seq_off = np.zeros(n + 1, np.int64)
     seq_off[1:] = np.cumsum(L)
@@ -1226,11 +1230,12 @@ def duplex_records(cons, raw: R.RawRecords, prefix: str, threads: int = 0, molec
         src = np.ascontiguousarray(src, np.uint8)
         if n:
             lib.bsdc_rows_gather(n, _ptr(rows), _ptr(L), int(stride), _ptr(src), _ptr(seq_off), _ptr(dst), int(threads))
-    return OutRecordsBam(
+    recs = OutRecordsBam(
         flag=np.tile(np.asarray([77, 141], np.uint16), F), tid=np.full(n, -1, np.int32), pos=np.full(n, -1, np.int32),
         mapq=np.zeros(n, np.uint8), next_tid=np.full(n, -1, np.int32), next_pos=np.full(n, -1, np.int32),
         tlen=np.zeros(n, np.int32), names=names_t, cig_off=np.zeros(n + 1, np.int64),
         cigar=np.zeros(0, np.uint32), seq_off=seq_off, seq=seq, qual=qual, aux=auxs_t, aux2=tg)
+    return recs if pool is None else (recs, tags_buf)
 
 
 def consensus_sharded(eng, raw: R.RawRecords, tags: bool, batch_bases: Optional[int] = None, dist=None,
@@ -1280,582 +1285,23 @@ def step5(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, prefix: 
             eng.close()
     if cons is None:  # not rank 0
         return {"records_in": raw.n}
-    recs = duplex_records(cons, raw, read_name_prefix(header) if prefix is None else prefix, threads)
+    return _write_consensus(cons, raw, raw.n, header, prefix, out_bam, fastq, level, threads, False, filter)
+
+
+def _write_consensus(cons, raw, n_in: int, header, prefix, out_bam, fastq, level, threads, molecular, flt) -> dict:
+    """The whole-file steps' tail: the consensus' records -> the BAM and / or the FASTQ pair ->
+    the info dict (with the `filter` entry of a filtered consensus)."""
+    recs = duplex_records(cons, raw, read_name_prefix(header) if prefix is None else prefix, threads,
+                          molecular=molecular)
     if out_bam is not None:
         write_bam(out_bam, output_header(header), recs, level, threads)
     if fastq is not None:
         write_fastq(fastq[0], fastq[1], recs, level, threads)
-    return _with_filter({"records_in": raw.n, "families": int(cons.status.shape[0]),
-                         "families_emitted": int(((cons.status & 1) != 0).sum()), "records_out": recs.n}, cons, filter)
-
-
-def _with_filter(info: dict, cons, flt) -> dict:
-    """info plus the `filter` entry of a filtered consensus."""
+    info = {"records_in": n_in, "families": int(cons.status.shape[0]),
+            "families_emitted": int(((cons.status & 1) != 0).sum()), "records_out": recs.n}
     if flt is not None:
         info["filter"] = _filter.summary(cons)
     return info
-
-
-def step5_stream(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, prefix: Optional[str] = None,
-                 threads: int = 0, level: int = 6, fastq: Optional[Tuple[str, str]] = None, tags: bool = True,
-                 chunk_bytes: int = DEFAULT_CHUNK_BYTES, slack: int = DEFAULT_SLACK,
-                 batch_bases: Optional[int] = None, stats: Optional[dict] = None, gpu_bgzf: bool = False,
-                 defer: Optional[int] = None, read_size: int = 8 << 20, filter=None) -> dict:
-    """step5 in bounded memory, pipelined (_stream_step); defer: the span past which a template is
-    deferred (default DEFAULT_DEFER_SPAN; 0 = off); read_size: compressed bytes per refill;
-    filter: as step5's."""
-    return _public(_stream_step(in_bam, fasta, out_bam, engine, prefix, threads, level, fastq, tags, chunk_bytes,
-                                slack, batch_bases, stats, gpu_bgzf, None, defer=defer, read_size=read_size,
-                                flt=filter))
-
-
-def molecular_stream(in_bam: str, out_bam: Optional[str], engine=None, prefix: Optional[str] = None, threads: int = 0,
-                     level: int = 6, fastq: Optional[Tuple[str, str]] = None, tags: bool = True,
-                     chunk_bytes: int = DEFAULT_CHUNK_BYTES, batch_bases: Optional[int] = None,
-                     stats: Optional[dict] = None, gpu_bgzf: bool = False, min_consensus_base_quality: int = 0,
-                     filter=None) -> dict:
-    """Rule call_consensus_reads_molecular (main.snake.py:46-55) in bounded memory: the same
-    pipeline as step5_stream over a GroupReadsByUmi-ordered input cut between MI runs
-    (stream_chunks(runs=True)); each chunk's runs are its consensus families (pipeline.molecular_records,
-    the vote alone, --min-consensus-base-quality applied).  The output is byte-identical to
-    molecular()'s whole-file path: no run straddles two chunks.  The reference's rule needs -Xmx100g
-    (main.snake.py:54, README.md:83); this holds about six chunks."""
-    return _public(_stream_step(in_bam, None, out_bam, engine, prefix, threads, level, fastq, tags, chunk_bytes,
-                                DEFAULT_SLACK, batch_bases, stats, gpu_bgzf, int(min_consensus_base_quality),
-                                flt=filter))
-
-
-def _public(info: dict) -> dict:
-    """The stream's info as the CLI prints it (JSON): the spliced keys become their count"""
-    sp = info.pop("splices", None)
-    info["spliced_families"] = 0 if sp is None else int(len(sp))
-    return info
-
-
-MINKEY = -(1 << 62)  # sort key of the pieces before every family (the header, a first range's start)
-
-
-def _family_cuts(cons, raw, plan, splices, strict: bool, start: int = 0):
-    """Output record indices where a chunk's BAM / FASTQ output is cut before each splice key, in
-    order: (record index, key) per key used.  A family's key is its first record's coarse key
-    (RawRecords.tc_key).  strict (the main stream): before the first family whose key exceeds the
-    splice (no family lies within kDeferMargin of one); else (the spill's pass): before the first
-    family whose key reaches the splice minus kDeferMargin (a deferred template's two records may
-    estimate its key a few positions apart).  splices[start:] are tried; a key no family of the
-    chunk reaches is left (-> cuts, the index of the first key left)."""
-    F = int(cons.status.shape[0])
-    if F == 0 or splices.shape[0] <= start:
-        return [], start
-    first = plan.order[plan.fam_off[:-1]]
-    k0, k1 = raw.tc_key[first, 0], raw.tc_key[first, 1]
-    em = np.zeros(F + 1, np.int64)
-    em[1:] = np.cumsum(_filter.kept(cons))
-    out, lo, j = [], 0, start
-    while j < splices.shape[0]:
-        s0, s1 = int(splices[j, 0]), int(splices[j, 1]) - (0 if strict else DEFER_MARGIN)
-        hit = (k0 > s0) | ((k0 == s0) & ((k1 > s1) if strict else (k1 >= s1)))
-        hit[:lo] = False
-        if not hit.any():
-            if not strict:  # (the pass's later chunks take it)
-                break
-            f = F
-        else:
-            f = int(np.argmax(hit))
-        lo = max(lo, f)
-        out.append((2 * int(em[lo]), (int(splices[j, 0]), int(splices[j, 1]))))
-        j += 1
-    return out, j
-
-
-def _region_cuts(cons, raw, plan, prev: list) -> list:
-    """Output record indices where a chunk's output is cut before the first family of each new key
-    contig pair (a family's key: its first record's coarse key), keyed (pair, MINKEY); prev[0] =
-    the pair of the family before the chunk (at first: that of the range's first piece's key)."""
-    first = plan.order[plan.fam_off[:-1]]
-    k0 = raw.tc_key[first, 0]
-    em = np.zeros(k0.shape[0] + 1, np.int64)
-    em[1:] = np.cumsum(_filter.kept(cons))
-    before = np.empty_like(k0)
-    before[0] = k0[0] if prev[0] is None else prev[0]
-    before[1:] = k0[:-1]
-    prev[0] = int(k0[-1])
-    return [(2 * int(em[f]), (int(k0[f]), MINKEY)) for f in np.nonzero(k0 != before)[0]]
-
-
-def _slice_records(recs: "OutRecordsBam", a: int, b: int) -> "OutRecordsBam":
-    """Records a..b-1 as views (the encoders index the ragged fields by absolute offsets)."""
-    return OutRecordsBam(flag=recs.flag[a:b], tid=recs.tid[a:b], pos=recs.pos[a:b], mapq=recs.mapq[a:b],
-                         next_tid=recs.next_tid[a:b], next_pos=recs.next_pos[a:b], tlen=recs.tlen[a:b],
-                         names=StringTable(recs.names.buf, recs.names.off[a:b + 1]), cig_off=recs.cig_off[a:b + 1],
-                         cigar=recs.cigar, seq_off=recs.seq_off[a:b + 1], seq=recs.seq, qual=recs.qual,
-                         aux=StringTable(recs.aux.buf, recs.aux.off[a:b + 1]),
-                         aux2=StringTable(recs.aux2.buf, recs.aux2.off[a:b + 1]) if recs.aux2 is not None else None)
-
-
-def pieces_of(marks, paths, phase: int, rank: int) -> list:
-    """One output's pieces between its marks (_stream_step): (sort key, phase, rank, index, paths,
-    starts, ends), ends of the last piece = the files' sizes."""
-    out = []
-    size = [os.path.getsize(x) if x else 0 for x in paths]
-    for i, (offs, key) in enumerate(marks):
-        end = list(marks[i + 1][0]) if i + 1 < len(marks) else size
-        out.append((tuple(key), phase, rank, i, list(paths), list(offs), end))
-    return out
-
-
-def assemble(dst: str, pieces, k: int):
-    """Output file k (0 the BAM, 1 / 2 the FASTQ pair) from the pieces in sort-key order, then one
-    BGZF EOF block; written aside and renamed over dst."""
-    tmp = dst + ".asm"
-    with open(tmp, "wb") as out:
-        for p in sorted(pieces, key=lambda x: (x[0], x[1], x[2], x[3])):
-            path, a, b = p[4][k], p[5][k], p[6][k]
-            if path is None or b <= a:
-                continue
-            with open(path, "rb") as f:
-                f.seek(a)
-                left = b - a
-                while left > 0:
-                    buf = f.read(min(left, 1 << 24))
-                    if not buf:
-                        raise RuntimeError("%s: short piece" % path)
-                    out.write(buf)
-                    left -= len(buf)
-        out.write(EOF_BLOCK)
-    os.replace(tmp, dst)
-
-
-EOF_BLOCK = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
-
-
-def write_spill_bam(dst: str, header: "BamHeader", spills: Sequence[str], level: int = 1, threads: int = 0) -> int:
-    """The spill files' records (bsdc_bam_stream_spill entries) in file order as a BAM -> records."""
-    data = b"".join(open(x, "rb").read() for x in spills if x and os.path.exists(x))
-    recs, n = spill_sorted_records(data)
-    del data
-    w = BamWriter(dst, header, level)
-    try:
-        w.add_raw(recs, threads)
-    finally:
-        w.close(threads)
-    return n
-
-
-def _stream_step(in_bam: str, fasta: Optional[str], out_bam: Optional[str], engine, prefix: Optional[str],
-                 threads: int, level: int, fastq: Optional[Tuple[str, str]], tags: bool, chunk_bytes: int, slack: int,
-                 batch_bases: Optional[int], stats: Optional[dict], gpu_bgzf: bool,
-                 molecular: Optional[int], rng=None, fragment: Optional[str] = None, runner=None,
-                 range_stats: Optional[dict] = None, owner=None, spill: Optional[str] = None,
-                 marks: Optional[list] = None, defer: Optional[int] = None, late_splices=None,
-                 first_key=None, read_size: int = 8 << 20, regions: bool = False, flt=None) -> dict:
-    """step5 (molecular None) or step 1 (molecular = its --min-consensus-base-quality) in bounded
-    memory, pipelined: a decoder thread cuts the next chunk of the
-    coordinate-sorted input (stream_bam: inflate, split where no template or MI family straddles),
-    a reader thread parses the chunk before, a planner thread forms the families of the one before
-    that (C++ plan) and materializes its batches into pinned memory; this thread uploads a chunk's
-    batches and runs them on the GPU; a builder thread builds
-    the output records of the chunk before and a writer thread appends them to the BAM
-    (BamWriter).  Peak host memory is about six chunks, whatever the file size.  The output is
-    byte-identical to step5's (tests/test_stream.py): every chunk's TemplateCoordinate keys sort
-    before the next chunk's, so the chunks' families in order are the whole file's.  gpu_bgzf: the
-    BAM's and the FASTQ pair's blocks are deflated on the engine's GPU (GpuBgzf; the same records,
-    other compressed bytes, files ≈4% larger).
-    Deferred templates (step 5; defer = the span, default DEFAULT_DEFER_SPAN, 0 = off): a template
-    whose other end lies far away or on another contig (bsdc_bam_stream_set_defer) would hold every
-    family after its key in memory until the stream reaches that end.  Its records go to a spill
-    file instead (with every family that may interleave with it), and the output is cut, at every
-    deferred key, into pieces (marks).  At the end a second pass runs the spill's records (in file
-    order, their own BAM; memory as their count) with the same keys (late_splices: each cut before
-    the first family that reaches the key), and the pieces of both are assembled in key order: the
-    same records as the whole file's.  Without deferred templates the output is written in place,
-    as it always was.
-    rank-parallel use (ranks.py): rng = the record range of the input to run (stream_chunks),
-    range_stats its statistics once read, fragment = "first" / "next" (the output pieces a rank
-    writes: BamWriter, FastqWriter), runner = a fleet-style runner (run_batch / run_chunk; the CPU
-    stand-in of the tests) instead of an Engine, owner = the rank's key interval (stream_chunks),
-    spill = the file the deferred records go to, marks = a list that receives the output's cut
-    points ((BAM offset, FASTQ offsets x 2), sort key of the piece that starts there): ranks.py
-    runs the second pass and the assembly; first_key = the sort key of the rank's first piece;
-    regions (the ranks' passes) = also cut before the first family of every new key contig pair
-    (a piece keyed (pair, MINKEY)): a rank does not register cross keys (bsdc_io.cpp), so the
-    deferred families of a contig's cross keys go between those pieces.
-    flt (filter.FilterParams): every batch is filtered on the device after its vote (step5's
-    `filter`); an Engine stream only."""
-    import queue
-    import threading
-    import time
-
-    from . import pipeline
-    own = engine is None and runner is None
-    # (a rank's engine may still be loading: ranks._LazyEngine; torch is imported with it)
-    lazy = bool(getattr(engine, "lazy", False))
-    if runner is None:
-        if own:
-            from .device import Engine
-        eng = Engine(0) if own else engine
-    else:
-        eng = None
-        if gpu_bgzf or molecular is not None or flt is not None:
-            raise ValueError("a runner stream: step 5 with host deflate only, unfiltered")
-    chunks: "queue.Queue" = queue.Queue(maxsize=1)
-    outs: "queue.Queue" = queue.Queue(maxsize=1)
-    err: list = []
-    info = {"records_in": 0, "families": 0, "families_emitted": 0, "records_out": 0, "chunks": 0,
-            "spilled_bytes": 0, "deferred_families": 0, "splices": []}
-    if flt is not None:
-        info["filter"] = _filter.empty_summary()
-    # deferral (step 5): the spill file and the output's pieces
-    dspan = 0 if molecular is not None else (DEFAULT_DEFER_SPAN if defer is None else int(defer))
-    late = None if late_splices is None else np.asarray(late_splices, np.int64).reshape(-1, 2)
-    lj = [0]  # (the spill's pass: the first deferred key not yet cut at)
-    rk_prev = [None]  # (regions: the key contig pair of the last family written; set with k_first)
-    tie = 0 if late is not None else 1  # (a spill piece sorts before the stream's piece of its key)
-    solo = marks is None and late is None  # this call runs the spill's pass and the assembly itself
-    mk = [] if marks is None else marks
-    frag = "first" if (solo and dspan) else fragment
-    # (the spill pass's first piece, before its first key, is empty: after the header in any case)
-    k_first = tuple(first_key) if first_key is not None else (MINKEY, 0, 2 if late is not None else 1)
-    rk_prev[0] = int(k_first[0])  # (a range whose first family lies in a later contig pair: cut before it)
-    out0 = out_bam if out_bam is not None else fastq[0]
-    spill_path = spill if spill is not None else \
-        (os.path.join(os.path.dirname(os.path.abspath(out0)), ".%s.%d.%x.spill" % (os.path.basename(out0), os.getpid(),
-                                                                                  id(info))) if dspan else None)
-    splices_tail: list = []
-    T = {"decode": 0.0, "plan": 0.0, "materialize": 0.0, "gpu": 0.0, "records": 0.0, "encode": 0.0,
-         "gpu_wait": 0.0, "writer_wait": 0.0}
-    G: dict = {}  # the GPU stage's host steps (pipeline.run_batches timing)
-    R_: dict = {}  # the reader's steps (StreamChunk.decode timing)
-    bufs = BufferPool()  # a chunk's record arrays, given back once its output is written
-    first = {}
-    stop = threading.Event()  # set on any failure: the decoder and planner stop at their next chunk
-
-    raws: "queue.Queue" = queue.Queue(maxsize=1)
-
-    def decoder():  # cuts the next chunk (inflate, split, family-complete selection) while the
-        # reader thread parses the one before
-        it = sw = None
-        rs = range_stats if range_stats is not None else {}
-        try:
-            if dspan:
-                sw = open(spill_path, "wb")
-            it = stream_chunks(in_bam, threads, chunk_bytes, slack, read_size, runs=molecular is not None, rng=rng,
-                               stats=rs, owner=owner, defer=dspan, keys=late is not None)
-            while not stop.is_set():
-                t0 = time.perf_counter()
-                nxt = next(it, None)
-                T["decode"] += time.perf_counter() - t0
-                if nxt is None:
-                    break
-                if sw is not None and nxt.spill:
-                    sw.write(nxt.spill)
-                    info["spilled_bytes"] += len(nxt.spill)
-                raws.put(nxt)
-            if not stop.is_set():
-                info["deferred_families"] = int(rs.get("deferred", 0))
-                info["peak_buffered"] = int(rs.get("peak_buffered", 0))
-            if sw is not None and not stop.is_set():
-                tail = rs.pop("spill_tail", b"")
-                sw.write(tail)
-                info["spilled_bytes"] += len(tail)
-                splices_tail.append(rs.pop("splices_tail", np.zeros((0, 2), np.int64)))
-        except BaseException as e:  # noqa: BLE001 -- handed to the main thread
-            err.append(e)
-            stop.set()
-        finally:
-            if sw is not None:
-                sw.close()
-            if it is not None:
-                it.close()  # (the stream is freed once every chunk is back)
-            raws.put(None)
-
-    parsed: "queue.Queue" = queue.Queue(maxsize=1)
-
-    def reader():  # parses a chunk's records while the planner forms the families of the one before
-        try:
-            while True:
-                ch = raws.get()
-                if ch is None:
-                    break
-                if stop.is_set():
-                    ch.discard()
-                    continue  # drain to the decoder's None without parsing
-                raw = ch.decode(threads, R_, bufs)[1]
-                raw._splices = ch.splices  # (the deferred keys this chunk's output is cut before)
-                parsed.put(raw)
-        except BaseException as e:  # noqa: BLE001 -- handed to the main thread
-            err.append(e)
-            stop.set()
-            while True:  # let the decoder finish
-                ch = raws.get()
-                if ch is None:
-                    break
-                ch.discard()
-        finally:
-            parsed.put(None)
-
-    # the planner materializes chunk k's batches into pool k % 3: chunk k - 3 is done on the GPU
-    # by then (the planner handed chunk k - 1 over only after the GPU stage took chunk k - 2).  A
-    # loading engine's first chunks materialize into plain host arrays, the pools come with it
-    def new_pools():
-        from .device import PinnedPool
-        return [PinnedPool() for _ in range(3)]
-    pools = None if runner is not None else ([] if lazy else new_pools())
-
-    def planner():  # forms a chunk's families and materializes its batches ahead of the GPU stage
-        try:
-            k = 0
-            while True:
-                raw = parsed.get()
-                if raw is None:
-                    break
-                if stop.is_set():
-                    continue  # drain to the reader's None without planning
-                t0 = time.perf_counter()
-                buf = raw._pool_buf
-                if molecular is None:
-                    plan = pipeline.plan_families(raw, "full", first["ref"])
-                else:  # step 1: the chunk's MI runs are the families, the vote alone
-                    raw = pipeline.molecular_records(raw)
-                    plan = pipeline.plan_families(raw, "vote", family_order="mi-group")
-                raw._pool_buf = buf
-                t1 = time.perf_counter()
-                fbs = None
-                if not plan.split_ext:
-                    images = None
-                    if pools is not None and not pools and eng.ready():
-                        pools.extend(new_pools())
-                    if pools:
-                        pool = pools[k % 3]
-                        k += 1
-                        pool.reset()
-                        images = pool.images
-                    fbs = pipeline.materialize_ranges(plan, pipeline.plan_ranges(plan, batch_bases), images)
-                T["plan"] += t1 - t0
-                T["materialize"] += time.perf_counter() - t1
-                chunks.put((raw, plan, fbs))
-        except BaseException as e:  # noqa: BLE001 -- handed to the main thread
-            err.append(e)
-            stop.set()
-            while parsed.get() is not None:  # let the reader finish
-                pass
-        finally:
-            chunks.put(None)
-
-    recq: "queue.Queue" = queue.Queue(maxsize=1)  # built records -> encoder
-
-    def builder():  # the output records of a chunk, while the encoder compresses the one before
-        try:
-            while True:
-                t0 = time.perf_counter()
-                item = outs.get()
-                T["writer_wait"] += time.perf_counter() - t0
-                if item is None:
-                    break
-                cons, raw, cuts = item
-                t0 = time.perf_counter()
-                recs = duplex_records(cons, raw, first["prefix"], threads, molecular=molecular is not None, pool=bufs)
-                T["records"] += time.perf_counter() - t0
-                back = [raw._pool_buf, getattr(recs.aux2, "_pool_buf", None)]
-                del item, cons, raw
-                recq.put((recs, back, cuts))
-        except BaseException as e:  # noqa: BLE001
-            err.append(e)
-            stop.set()
-            while outs.get() is not None:  # drain so the main thread never blocks
-                pass
-        finally:
-            recq.put(None)
-
-    def writer():
-        w = fq = None
-        try:
-            gz = GpuBgzf(eng.device) if gpu_bgzf and out_bam is not None else None
-            gzf = GpuBgzf(eng.device) if gpu_bgzf and fastq is not None else None  # (one job in flight each)
-            w = BamWriter(out_bam, output_header(first["header"]), level, gz, frag) if out_bam is not None else None
-            fq = FastqWriter(fastq[0], fastq[1], level, gzf, frag is not None) if fastq is not None else None
-
-            def cut(key):  # everything so far leaves as whole blocks; a piece with this key starts here
-                bo = w.flush(threads) if w is not None else 0
-                fo = fq.flush(threads) if fq is not None else (0, 0)
-                mk.append(((bo, fo[0], fo[1]), key))
-            mk.append(((0, 0, 0), k_first))  # (a first piece holds the header, if any)
-            while True:
-                item = recq.get()
-                if item is None:
-                    break
-                recs, back, cuts = item
-                t1 = time.perf_counter()
-                a = 0
-                for idx, key in cuts + [(recs.n, None)]:
-                    part = recs if (a == 0 and idx == recs.n) else _slice_records(recs, a, idx)
-                    if idx > a:
-                        if w is not None:
-                            w.add(part, threads)
-                        if fq is not None:
-                            fq.add(part, threads)
-                    if key is not None:
-                        cut((key[0], key[1], tie))
-                    a = idx
-                info["records_out"] += recs.n
-                T["encode"] += time.perf_counter() - t1
-                del item, recs
-                for buf in back:  # (the chunk's records are written; nothing refers to their arrays)
-                    bufs.give(buf)
-            if w is not None:
-                w.close(threads)
-            if fq is not None:
-                fq.close(threads)
-        except BaseException as e:  # noqa: BLE001
-            err.append(e)
-            stop.set()
-            close_quietly(w, fq)
-            while recq.get() is not None:  # drain so the builder never blocks
-                pass
-
-    # the header and the reference come first: the plan of a chunk needs the reference
-    hdr0 = read_bam_header(in_bam)
-    first["header"] = hdr0
-    ref = read_fasta(fasta, hdr0) if molecular is None else None  # (step 1 converts nothing)
-    first["ref"] = ref
-    first["prefix"] = read_name_prefix(hdr0) if prefix is None else prefix
-    import contextlib
-    flags = contextlib.nullcontext() if molecular is None else eng.flags(min_consensus_base_quality=molecular)
-    try:
-        flags.__enter__()
-    except BaseException:
-        if own:
-            eng.close()
-        raise
-    try:
-        if ref is not None:
-            (runner if runner is not None else eng).load_reference(ref)
-        td = threading.Thread(target=decoder, daemon=True)
-        tr = threading.Thread(target=reader, daemon=True)
-        tp = threading.Thread(target=planner, daemon=True)
-        tb = threading.Thread(target=builder, daemon=True)
-        tw = threading.Thread(target=writer, daemon=True)
-        td.start()
-        tr.start()
-        tp.start()
-        tb.start()
-        tw.start()
-        mode = pipeline.MODE_CONVERT | pipeline.MODE_EXTEND | pipeline.MODE_VOTE if molecular is None else pipeline.MODE_VOTE
-        drained = False
-        try:
-            while True:
-                t0 = time.perf_counter()
-                item = chunks.get()
-                T["gpu_wait"] += time.perf_counter() - t0
-                if item is None:
-                    drained = True
-                    break
-                if stop.is_set():  # another stage failed: stop working, drain below
-                    break
-                raw, plan, fbs = item
-                t0 = time.perf_counter()
-                tg = tags and out_bam is not None  # the FASTQ pair carries no tags
-                if runner is not None:
-                    if fbs is None:
-                        cons = runner.run_chunk(raw, tg, batch_bases)
-                    else:
-                        parts = []
-                        for fb in fbs:
-                            sub = R.take(raw, fb.src) if getattr(runner, "needs_raw", False) else None
-                            parts.append(pipeline.consensus_from_output(fb, runner.run_batch(fb, mode, tg, sub)))
-                        cons = pipeline.concat_consensus(parts)
-                        del fbs, parts
-                elif fbs is None:
-                    cons = pipeline.run_step5(eng, raw, tags=tg, batch_bases=batch_bases, filter=flt)[0]
-                else:
-                    fkw = {} if flt is None else {"filter": flt, "molecular": molecular is not None}
-                    cons = pipeline.concat_consensus(pipeline.run_batches(eng, fbs, mode, tg, G, **fkw))
-                    del fbs
-                T["gpu"] += time.perf_counter() - t0
-                info["records_in"] += raw.n
-                info["families"] += int(cons.status.shape[0])
-                info["families_emitted"] += int(((cons.status & 1) != 0).sum())
-                info["chunks"] += 1
-                if flt is not None:
-                    info["filter"] = _filter.add_summary(info["filter"], _filter.summary(cons))
-                cuts = []
-                if late is not None:  # the spill's pass: cut before the families of each deferred key
-                    cuts, lj[0] = _family_cuts(cons, raw, plan, late, False, lj[0])
-                elif getattr(raw, "_splices", None) is not None and raw._splices.shape[0]:
-                    cuts, _ = _family_cuts(cons, raw, plan, raw._splices, True)
-                    info["splices"].append(raw._splices)
-                if regions and cons.status.shape[0]:
-                    cuts = sorted(cuts + _region_cuts(cons, raw, plan, rk_prev))
-                outs.put((cons, raw, cuts))
-        except BaseException:
-            stop.set()
-            raise
-        finally:
-            if not drained:  # let the planner finish (it stops planning once `stop` is set)
-                stop.set()
-                while chunks.get() is not None:
-                    pass
-            outs.put(None)
-            tb.join()
-            tw.join()
-            tp.join()
-            tr.join()
-            td.join()
-        if not err:
-            info["splices"] = np.concatenate(info["splices"] + splices_tail + [np.zeros((0, 2), np.int64)]) \
-                if dspan else np.zeros((0, 2), np.int64)
-            if solo and dspan:  # the deferred templates' pass and the assembly (or just the EOF blocks)
-                _finish_deferred(in_bam, fasta, out_bam, fastq, eng if runner is None else None, runner, first["prefix"],
-                                 threads, level, tags, chunk_bytes, slack, batch_bases, gpu_bgzf, mk, spill_path, info,
-                                 flt)
-    finally:
-        flags.__exit__(None, None, None)
-        if own:
-            eng.close()
-        if solo and spill_path is not None and os.path.exists(spill_path):
-            os.unlink(spill_path)
-    if err:
-        raise err[0]
-    if stats is not None:
-        stats.update({k: round(v, 4) for k, v in T.items()})
-        stats.update({"gpu_" + k: round(v, 4) for k, v in G.items()})
-        stats.update({"reader_" + k: round(v, 4) for k, v in R_.items()})
-    return info
-
-
-def _finish_deferred(in_bam, fasta, out_bam, fastq, eng, runner, prefix, threads, level, tags, chunk_bytes, slack,
-                     batch_bases, gpu_bgzf, marks, spill_path, info, flt=None):
-    """One process's deferred templates: with none, the EOF blocks the fragment-mode writers left
-    out; else the spill's records as their own BAM through the stream (no deferral; cut at every
-    deferred key), then the pieces of both outputs assembled in key order."""
-    paths = [out_bam, fastq[0] if fastq else None, fastq[1] if fastq else None]
-    if info["splices"].shape[0] == 0 and info["spilled_bytes"] == 0:
-        for x in paths:
-            if x is not None:
-                with open(x, "ab") as f:
-                    f.write(EOF_BLOCK)
-        return
-    base = spill_path + ".p2"
-    sb = base + ".bam"
-    p2 = [base + ".out.bam" if out_bam is not None else None,
-          base + ".1.fq.gz" if fastq else None, base + ".2.fq.gz" if fastq else None]
-    try:
-        info["deferred_records"] = write_spill_bam(sb, read_bam_header(in_bam), [spill_path], 1, threads)
-        mk2: list = []
-        inf2 = _stream_step(sb, fasta, p2[0], eng, prefix, threads, level, (p2[1], p2[2]) if fastq else None, tags,
-                            chunk_bytes, slack, batch_bases, None, gpu_bgzf, None, fragment="next",
-                            runner=runner, marks=mk2, defer=0, late_splices=info["splices"], flt=flt)
-        for k in ("records_in", "families", "families_emitted", "records_out"):
-            info[k] += inf2[k]
-        if flt is not None:
-            info["filter"] = _filter.add_summary(info["filter"], inf2["filter"])
-        pieces = pieces_of(marks, paths, 0, 0) + pieces_of(mk2, p2, 1, 0)
-        for k in range(3):
-            if paths[k] is not None:
-                assemble(paths[k], pieces, k)
-    finally:
-        for x in [sb] + p2:
-            if x is not None and os.path.exists(x):
-                os.unlink(x)
 
 
 def molecular(in_bam: str, out_bam: Optional[str], engine=None, prefix: Optional[str] = None, threads: int = 0,
@@ -1875,10 +1321,13 @@ def molecular(in_bam: str, out_bam: Optional[str], engine=None, prefix: Optional
     finally:
         if own:
             eng.close()
-    recs = duplex_records(cons, rm, read_name_prefix(header) if prefix is None else prefix, threads, molecular=True)
-    if out_bam is not None:
-        write_bam(out_bam, output_header(header), recs, level, threads)
-    if fastq is not None:
-        write_fastq(fastq[0], fastq[1], recs, level, threads)
-    return _with_filter({"records_in": raw.n, "families": int(cons.status.shape[0]),
-                         "families_emitted": int(((cons.status & 1) != 0).sum()), "records_out": recs.n}, cons, filter)
+    return _write_consensus(cons, rm, raw.n, header, prefix, out_bam, fastq, level, threads, True, filter)
+
+
+def __getattr__(name):
+    """The streaming steps live in stream.py (which imports this module); they stay importable
+    from here."""
+    if name in ("step5_stream", "molecular_stream"):
+        from . import stream
+        return getattr(stream, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -2,9 +2,9 @@
 
 MI families are independent, so the GPUs never talk to each other.  This process
 (the coordinator) never touches a GPU.  It spawns one worker process per device, then runs the
-one-GPU stream's front end (bam.step5_stream): a decoder thread reads the coordinate-sorted BAM
-once, in bounded chunks (bam.stream_bam), and a planner thread forms each chunk's families
-(batch.plan_families, the fgbio TemplateCoordinate runs).  The coordinator cuts every chunk's
+one-GPU stream's front end (stream.FrontEnd): a decoder thread reads the coordinate-sorted BAM
+once, in bounded chunks (bam.stream_chunks), a reader thread parses them and a planner thread forms
+each chunk's families (batch.plan_families, the fgbio TemplateCoordinate runs).  The coordinator cuts every chunk's
 families into device batches (pipeline.plan_ranges), builds each batch (C++ materialize) and hands
 it to the least-loaded worker through shared memory: arrays travel as torch.multiprocessing
 named shared-memory segments, pooled and reused on both sides (SegmentPool): materialize writes
@@ -13,8 +13,8 @@ another, and only names and offsets are pickled (no process-group traffic).  A w
 the batch to its GPU, runs the kernels (libbsdc, the same launch as one GPU) and fetches the
 consensus arrays into a segment of its own, which the coordinator reads in place and releases
 once the chunk is written.  A collector thread puts the batches back in input order
-and a writer thread turns each complete chunk into records and appends them to the BAM / FASTQ
-(bam.duplex_records, BamWriter, FastqWriter): the output is byte-identical to the one-GPU stream.
+and the stream's back end (stream.BackEnd: a builder and a writer thread) turns each complete
+chunk into records and appends them to the BAM / FASTQ: the output is byte-identical to the one-GPU stream.
 
 Memory is bounded whatever the input size: at most `inflight` batches per worker, and the
 decoder / planner / writer hand-offs hold one chunk each (reference: the 100 GB note of
@@ -582,29 +582,165 @@ class _FamilyIndex:
         return int(self.fam_off.shape[0]) - 1
 
 
+def _segment_batches(cpool: "SegmentPool", plan, ranges) -> list:
+    """A chunk's batches (stream.FrontEnd's `build`), the family images straight into `cpool`'s
+    segments: per batch (it without its host bookkeeping, its _FamilyIndex, the segments it uses)."""
+    from . import pipeline
+    out = []
+    for a, b in ranges:
+        img = []
+
+        def images(n_slots: int):
+            ns = (n_slots // 2 + 255) // 256 * 256
+            img.append(cpool.take(ns + n_slots + 256))
+            buf = np.frombuffer(cpool.buf(img[-1]), np.uint8)
+            return buf[:ns], buf[ns:ns + n_slots]
+        fb = pipeline.materialize(plan, a, b, images=images)
+        index = _FamilyIndex(fb.fam_mi.copy(), fb.fam_off.astype(np.int64), fb.src.astype(np.int64))
+        # the worker needs the device arrays only (host bookkeeping stays here)
+        slim = dataclasses.replace(fb, src=np.zeros(0, np.int64), fam_mi=np.zeros(0, np.int32),
+                                   t2_rank=np.zeros(0, np.int64), rec_tid=np.zeros(0, np.int32))
+        out.append((slim, index, img))
+    return out
+
+
+class _Coordinator:
+    """The dealer (deal, on the caller's thread) and the collector (collect, a thread) between the
+    stream's two ends.  pend: chunk id -> {"chunk", "n" (batches; None until the dealer has sent
+    them all), "parts": {i: Consensus}, "index": {i: _FamilyIndex}, "in": {i: coordinator segments
+    of batch i}, "out": [(worker, its result segments)]}, filled by both; a bounded number of
+    chunks (2 * workers + 2) lies between the dealer and the writer."""
+
+    def __init__(self, fleet: "Fleet", cpool: "SegmentPool", views: "SegmentViews", stop: threading.Event,
+                 mode: int, tags: bool, batch_bases: Optional[int]):
+        self.fleet, self.cpool, self.views, self.stop = fleet, cpool, views, stop
+        self.mode, self.tags, self.batch_bases = mode, tags, batch_bases
+        self.pend, self.plock = {}, threading.Condition()
+        self.dealt, self.eof = 0, False  # chunks the dealer has taken; it has seen them all
+        self.T, self.info = {"submit_wait": 0.0}, {"families": 0, "families_emitted": 0, "batches": 0}
+
+    def wake(self):
+        with self.plock:
+            self.plock.notify_all()
+
+    def deal(self, ch):
+        """One planned chunk's batches (or the whole chunk, a split_ext plan) to the workers."""
+        fleet, cpool, stop, T, cid = self.fleet, self.cpool, self.stop, self.T, self.dealt
+        with self.plock:
+            while len(self.pend) >= 2 * fleet.n + 2 and not stop.is_set():
+                self.plock.wait(0.5)
+            entry = self.pend[cid] = {"chunk": ch, "n": None, "parts": {}, "index": {}, "in": {}, "out": []}
+        n = 0
+        if ch.batches is None:
+            t, segs = pack(ch.raw, cpool)
+            with self.plock:
+                entry["in"][0] = segs
+            if fleet.submit(("chunk", (cid, 0), t, self.tags, self.batch_bases), stop) >= 0:
+                n = 1
+        else:
+            for slim, index, img in ch.batches:
+                raw_sub = R.take(ch.raw, index.src) if fleet.needs_raw else None
+                t0 = time.perf_counter()
+                t, segs = pack(slim, cpool)
+                rt, rsegs = pack(raw_sub, cpool) if raw_sub is not None else (None, [])
+                T["pack"] = T.get("pack", 0.0) + time.perf_counter() - t0
+                with self.plock:
+                    entry["index"][n] = index
+                    entry["in"][n] = sorted(set(segs) | set(rsegs) | set(img))
+                t0 = time.perf_counter()
+                w = fleet.submit(("batch", (cid, n), t, self.mode, self.tags, rt), stop)
+                T["submit_wait"] += time.perf_counter() - t0
+                del slim, raw_sub
+                if w < 0:
+                    break
+                n += 1
+                self.info["batches"] += 1
+            ch.batches = None
+        with self.plock:
+            entry["n"] = n
+            self.dealt += 1
+            self.plock.notify_all()
+
+    def finish(self):
+        with self.plock:
+            self.eof = True
+            self.plock.notify_all()
+
+    def collect(self, fault, back):
+        """Worker results -> pend; complete chunks go to the back end in input order."""
+        from . import pipeline
+        fleet, pend, nxt = self.fleet, self.pend, 0
+        try:
+            while not self.stop.is_set():
+                ready = []
+                with self.plock:
+                    while nxt in pend and pend[nxt]["n"] is not None and len(pend[nxt]["parts"]) == pend[nxt]["n"]:
+                        ready.append(pend.pop(nxt))
+                        nxt += 1
+                    if ready:
+                        self.plock.notify_all()
+                    finished = self.eof and nxt >= self.dealt
+                for c in ready:
+                    cons = pipeline.concat_consensus([c["parts"][i] for i in range(c["n"])])
+                    self.info["families"] += int(cons.status.shape[0])
+                    self.info["families_emitted"] += int(((cons.status & 1) != 0).sum())
+                    c["chunk"].results = c["out"]
+                    back.put(cons, c["chunk"])
+                del ready
+                if finished:
+                    break
+                m = fleet.get(timeout=0.5)
+                if m is None:
+                    continue
+                if m[0] == "forget":  # a worker dropped one of its result segments
+                    self.views.forget(m[2])
+                    continue
+                kind, wid, (cid, i), res = m[0], m[1], m[2], unpack(m[3], self.views)
+                for k, v in m[5].items():  # (the workers' busy time, summed)
+                    self.T[k] = self.T.get(k, 0.0) + v
+                with self.plock:
+                    c = pend[cid]
+                    c["parts"][i] = pipeline.consensus_from_output(c["index"].pop(i), res) if kind == "batch" else res
+                    c["out"].append((wid, m[4]))
+                    back_segs = c["in"].pop(i, ())
+                    self.plock.notify_all()
+                for name in back_segs:  # (the worker has read the batch: its result is back)
+                    self.cpool.give(name)
+                fleet.done(wid)
+        except BaseException as e:  # noqa: BLE001
+            fault(e)
+
+    def release(self, chunk):
+        """stream.BackEnd's on_written: nothing refers to the workers' result segments any more."""
+        for wid, names in chunk.results:
+            for name in names:
+                self.fleet.tqs[wid].put(("release", name))
+
+
 def step5_stream_multi(in_bam: str, fasta: str, out_bam: Optional[str], devices: Sequence[int],
                        prefix: Optional[str] = None, threads: int = 0, level: int = 6,
                        fastq: Optional[Tuple[str, str]] = None, tags: bool = True, chunk_bytes: Optional[int] = None,
                        slack: Optional[int] = None, batch_bases: Optional[int] = None, inflight: int = 2,
                        runner: Optional[str] = None, stats: Optional[dict] = None, gpu_bgzf: bool = False,
                        fleet: Optional["Fleet"] = None) -> dict:
-    """bam.step5_stream over len(devices) GPU workers (see the module docstring).  Same file
-    contract and output bytes as bam.step5 / bam.step5_stream (main.snake.py:121-164).
+    """bam.step5_stream over len(devices) GPU workers (see the module docstring): the stream's
+    front end and back end (stream.FrontEnd, stream.BackEnd) with the dealer and the collector
+    between them instead of a GPU stage.  Same file contract and output bytes as bam.step5 /
+    bam.step5_stream (main.snake.py:121-164).
     gpu_bgzf: the writer deflates on devices[0] (bam.GpuBgzf; the coordinator touches that GPU
     only after its workers are spawned).  fleet: an already started Fleet over `devices` (left
     running; e.g. to time the stream without the workers' start-up), else one is started and
     closed here."""
-    from . import bam, pipeline
+    import functools
+
+    from . import bam, pipeline, stream
     chunk_bytes = bam.DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes
     slack = bam.DEFAULT_SLACK if slack is None else slack
-    T = {"decode": 0.0, "plan": 0.0, "materialize": 0.0, "submit_wait": 0.0, "records": 0.0, "encode": 0.0}
     info = {"records_in": 0, "families": 0, "families_emitted": 0, "records_out": 0, "chunks": 0, "batches": 0,
             "workers": len(devices)}
     hdr0 = bam.read_bam_header(in_bam)
     ref = bam.read_fasta(fasta, hdr0)
     pre = bam.read_name_prefix(hdr0) if prefix is None else prefix
-    tg = tags and out_bam is not None  # the FASTQ pair carries no tags
-    mode = pipeline.MODE_CONVERT | pipeline.MODE_EXTEND | pipeline.MODE_VOTE
     own_fleet = fleet is None
     fleet = Fleet(devices, runner, inflight) if own_fleet else fleet
     # batch images and messages; a batch's go back when its result arrives; a dropped one is
@@ -619,256 +755,33 @@ def step5_stream_multi(in_bam: str, fasta: str, out_bam: Optional[str], devices:
     cpool.prefill(nseg, int(1.25 * est) + 4096)
     cpool.prefill(nseg, SegmentPool.MIN)
     views = SegmentViews()  # the workers' result segments
-    stop = threading.Event()
-    err: List[BaseException] = []
-    raws: "queue.Queue" = queue.Queue(maxsize=1)
-    parsed: "queue.Queue" = queue.Queue(maxsize=1)
-    chunks: "queue.Queue" = queue.Queue(maxsize=1)
-    outs: "queue.Queue" = queue.Queue(maxsize=1)
-    # chunk id -> {"raw", "n" (batches; None until the dealer has sent them all), "parts": {i:
-    # Consensus}, "index": {i: _FamilyIndex}, "in": {i: coordinator segments of batch i}, "out":
-    # [(worker, its result segments)]}, filled by the dealer and the collector
-    pend: Dict[int, dict] = {}
-    eof: List[Optional[int]] = [None]  # number of chunks, once the dealer has seen them all
-    plock = threading.Condition()
-
-    def fail(e: BaseException):
-        err.append(e)
-        stop.set()
-        with plock:
-            plock.notify_all()
-
     bufs = bam.BufferPool()  # a chunk's record and tag arrays, given back once it is written
-    R_: dict = {}  # the reader's steps (StreamChunk.decode timing)
-
-    def decoder():  # cuts the next chunk while the planner decodes and plans the one before
-        it = None
-        try:
-            it = bam.stream_chunks(in_bam, threads, chunk_bytes, slack)
-            for ch in it:
-                if stop.is_set():
-                    ch.discard()
-                    break
-                raws.put(ch)
-        except BaseException as e:  # noqa: BLE001
-            fail(e)
-        finally:
-            if it is not None:
-                it.close()
-            raws.put(None)
-
-    def reader():  # parses a chunk's records while the planner forms the families of the one before
-        try:
-            while True:
-                t0 = time.perf_counter()
-                ch = raws.get()
-                if ch is None:
-                    break
-                if stop.is_set():
-                    ch.discard()
-                    continue  # drain to the decoder's None
-                t1 = time.perf_counter()
-                raw = ch.decode(threads, R_, bufs)[1]
-                T["parse"] = T.get("parse", 0.0) + time.perf_counter() - t1
-                T["decode"] += t1 - t0  # the wait for the decoder
-                parsed.put(raw)
-        except BaseException as e:  # noqa: BLE001
-            fail(e)
-            while True:
-                ch = raws.get()
-                if ch is None:
-                    break
-                ch.discard()
-        finally:
-            parsed.put(None)
-
-    def materialize(plan, a: int, b: int):
-        """-> (the batch without its host bookkeeping, its _FamilyIndex, the segments it uses)."""
-        img = []
-
-        def images(n_slots: int):  # the family images straight into a shared segment
-            ns = (n_slots // 2 + 255) // 256 * 256
-            img.append(cpool.take(ns + n_slots + 256))
-            buf = np.frombuffer(cpool.buf(img[-1]), np.uint8)
-            return buf[:ns], buf[ns:ns + n_slots]
-        fb = pipeline.materialize(plan, a, b, images=images)
-        index = _FamilyIndex(fb.fam_mi.copy(), fb.fam_off.astype(np.int64), fb.src.astype(np.int64))
-        # the worker needs the device arrays only (host bookkeeping stays here)
-        slim = dataclasses.replace(fb, src=np.zeros(0, np.int64), fam_mi=np.zeros(0, np.int32),
-                                   t2_rank=np.zeros(0, np.int64), rec_tid=np.zeros(0, np.int32))
-        return slim, index, img
-
-    def planner():  # forms a chunk's families and materializes its batches ahead of the dealer
-        try:
-            while True:
-                raw = parsed.get()
-                if raw is None:
-                    break
-                if stop.is_set():
-                    continue  # drain to the reader's None
-                t0 = time.perf_counter()
-                plan = pipeline.plan_families(raw, "full", ref)
-                t1 = time.perf_counter()
-                T["plan"] += t1 - t0
-                batches = None if plan.split_ext else [materialize(plan, a, b)
-                                                       for a, b in pipeline.plan_ranges(plan, batch_bases)]
-                T["materialize"] += time.perf_counter() - t1
-                chunks.put((raw, plan, batches))
-        except BaseException as e:  # noqa: BLE001
-            fail(e)
-            while parsed.get() is not None:
-                pass
-        finally:
-            chunks.put(None)
-
-    def collector():
-        """Worker results -> pend; complete chunks go to the writer in input order."""
-        nxt = 0
-        try:
-            while not stop.is_set():
-                ready = []
-                with plock:
-                    while nxt in pend and pend[nxt]["n"] is not None and len(pend[nxt]["parts"]) == pend[nxt]["n"]:
-                        ready.append(pend.pop(nxt))
-                        nxt += 1
-                    if ready:
-                        plock.notify_all()
-                    finished = eof[0] is not None and nxt >= eof[0]
-                for c in ready:
-                    outs.put(c)
-                if finished:
-                    break
-                m = fleet.get(timeout=0.5)
-                if m is None:
-                    continue
-                if m[0] == "forget":  # a worker dropped one of its result segments
-                    views.forget(m[2])
-                    continue
-                kind, wid, (cid, i), res = m[0], m[1], m[2], unpack(m[3], views)
-                for k, v in m[5].items():  # (the workers' busy time, summed)
-                    T[k] = T.get(k, 0.0) + v
-                with plock:
-                    c = pend[cid]
-                    c["parts"][i] = pipeline.consensus_from_output(c["index"].pop(i), res) if kind == "batch" else res
-                    c["out"].append((wid, m[4]))
-                    back = c["in"].pop(i, ())
-                    plock.notify_all()
-                for name in back:  # (the worker has read the batch: its result is back)
-                    cpool.give(name)
-                fleet.done(wid)
-        except BaseException as e:  # noqa: BLE001
-            fail(e)
-        finally:
-            outs.put(None)
-
-    def writer():
-        w = fq = None
-        try:
-            gz = bam.GpuBgzf(int(devices[0])) if gpu_bgzf and out_bam is not None else None
-            gzf = bam.GpuBgzf(int(devices[0])) if gpu_bgzf and fastq is not None else None
-            w = bam.BamWriter(out_bam, bam.output_header(hdr0), level, gz) if out_bam is not None else None
-            fq = bam.FastqWriter(fastq[0], fastq[1], level, gzf) if fastq is not None else None
-            while True:
-                c = outs.get()
-                if c is None:
-                    break
-                if stop.is_set():
-                    continue
-                cons = pipeline.concat_consensus([c["parts"][i] for i in range(c["n"])])
-                info["families"] += int(cons.status.shape[0])
-                info["families_emitted"] += int(((cons.status & 1) != 0).sum())
-                t0 = time.perf_counter()
-                recs = bam.duplex_records(cons, c["raw"], pre, threads, pool=bufs)
-                t1 = time.perf_counter()
-                if w is not None:
-                    w.add(recs, threads)
-                if fq is not None:
-                    fq.add(recs, threads)
-                info["records_out"] += recs.n
-                T["records"] += t1 - t0
-                T["encode"] += time.perf_counter() - t1
-                back = [getattr(c["raw"], "_pool_buf", None), getattr(recs.aux2, "_pool_buf", None)]
-                results = c["out"]
-                del c, cons, recs
-                for buf in back:  # (the chunk is written: nothing refers to its record arrays)
-                    bufs.give(buf)
-                for wid, names in results:  # nor to the workers' result segments
-                    for name in names:
-                        fleet.tqs[wid].put(("release", name))
-            if not stop.is_set():
-                if w is not None:
-                    w.close(threads)
-                if fq is not None:
-                    fq.close(threads)
-            else:
-                bam.close_quietly(w, fq)
-        except BaseException as e:  # noqa: BLE001
-            fail(e)
-            bam.close_quietly(w, fq)
-            while outs.get() is not None:
-                pass
-
-    workers = [threading.Thread(target=f, daemon=True) for f in (decoder, reader, planner, collector, writer)]
-    drained = False
+    fault = stream.Fault()
+    co = _Coordinator(fleet, cpool, views, fault.stop, pipeline.MODE_CONVERT | pipeline.MODE_EXTEND | pipeline.MODE_VOTE,
+                      tags and out_bam is not None, batch_bases)  # (the FASTQ pair carries no tags)
+    fault.on_fail = co.wake
+    front = stream.FrontEnd(fault, dict(path=in_bam, threads=threads, chunk_bytes=chunk_bytes, slack=slack),
+                            functools.partial(stream.plan_step5, ref=ref), functools.partial(_segment_batches, cpool),
+                            threads, batch_bases, bufs)
+    back = stream.BackEnd(fault, out_bam, fastq, hdr0, pre, threads, level, bufs,
+                          gz_device=(lambda: int(devices[0])) if gpu_bgzf else None, on_written=co.release)
+    collector = threading.Thread(target=co.collect, args=(fault, back), name="stream_collector", daemon=True)
     try:
         fleet.broadcast(("ref", pack(dataclasses.replace(ref, letters={}), cpool)[0]))
-        for t in workers:
-            t.start()
-        cid = 0
-        while not stop.is_set():
-            item = chunks.get()
-            if item is None:
-                drained = True
-                break
-            raw, plan, batches = item
-            info["records_in"] += raw.n
-            info["chunks"] += 1
-            with plock:  # a bounded number of chunks between the dealer and the writer
-                while len(pend) >= 2 * fleet.n + 2 and not stop.is_set():
-                    plock.wait(0.5)
-                pend[cid] = {"raw": raw, "n": None, "parts": {}, "index": {}, "in": {}, "out": []}
-            n = 0
-            if plan.split_ext:
-                t, segs = pack(raw, cpool)
-                with plock:
-                    pend[cid]["in"][0] = segs
-                if fleet.submit(("chunk", (cid, 0), t, tg, batch_bases), stop) >= 0:
-                    n = 1
-            else:
-                for slim, index, img in batches:
-                    raw_sub = R.take(raw, index.src) if fleet.needs_raw else None
-                    t0 = time.perf_counter()
-                    t, segs = pack(slim, cpool)
-                    rt, rsegs = pack(raw_sub, cpool) if raw_sub is not None else (None, [])
-                    T["pack"] = T.get("pack", 0.0) + time.perf_counter() - t0
-                    with plock:
-                        pend[cid]["index"][n] = index
-                        pend[cid]["in"][n] = sorted(set(segs) | set(rsegs) | set(img))
-                    t0 = time.perf_counter()
-                    w = fleet.submit(("batch", (cid, n), t, mode, tg, rt), stop)
-                    T["submit_wait"] += time.perf_counter() - t0
-                    del slim, raw_sub
-                    if w < 0:
-                        break
-                    n += 1
-                    info["batches"] += 1
-                del batches
-            with plock:
-                pend[cid]["n"] = n
-                plock.notify_all()
-            cid += 1
-        with plock:
-            eof[0] = cid
-            plock.notify_all()
-    except BaseException as e:  # noqa: BLE001
-        fail(e)
+        with front, back:
+            collector.start()
+            try:
+                for ch in front:
+                    info["records_in"] += ch.raw.n
+                    info["chunks"] += 1
+                    co.deal(ch)
+                    del ch
+                co.finish()
+            except BaseException as e:  # noqa: BLE001
+                fault(e)
+            finally:  # (the collector ends with the last chunk, or at `stop`)
+                collector.join(timeout=600)
     finally:
-        if not drained:  # let the planner and the decoder finish (they stop at their next chunk)
-            stop.set()
-            while chunks.get() is not None:
-                pass
-        for t in workers:
-            t.join(timeout=600)
         if own_fleet:
             fleet.close()
         else:  # (a kept fleet's workers may still hold this run's result segments: let them go)
@@ -876,11 +789,14 @@ def step5_stream_multi(in_bam: str, fasta: str, out_bam: Optional[str], devices:
                 fleet.tqs[wid].put(("drop",))
         views.close()
         cpool.close()
-    if err:
-        raise err[0]
+    if fault.errors:
+        raise fault.errors[0]
+    info.update(co.info, records_out=back.records_out)
     if stats is not None:
+        T = dict(co.T, decode=front.T["reader_wait"], parse=front.T["parse"], plan=front.T["plan"],
+                 materialize=front.T["materialize"], records=back.T["records"], encode=back.T["encode"])
         stats.update({k: round(v, 4) for k, v in T.items()})
-        stats.update({"reader_" + k: round(v, 4) for k, v in R_.items()})
+        stats.update({"reader_" + k: round(v, 4) for k, v in front.R.items()})
         stats["segments_created"] = cpool.n
         stats["segments_created_MiB"] = round(cpool.created_bytes / 2**20, 1)
     return info

@@ -256,39 +256,19 @@ def plan_ranges(plan: FamilyPlan, batch_bases: Optional[int] = None):
 def run_ranges(engine: Engine, plan: FamilyPlan, ranges, mode: int, tags: bool = False,
                timing: Optional[dict] = None, filter: Optional[FilterParams] = None,
                molecular: bool = False) -> List[Consensus]:
-    """Plan family ranges through the kernels, one launch each, output per range in range order.
-    The host builds range i + 1 while the kernels of range i run.  `timing`: seconds added per
-    host step (materialize, upload, fetch = wait + copy out, unpack).  `filter`: each range is
-    filtered on the device after its vote (Engine.filter; `molecular`: step-1 records), which
-    needs the tags' rows there; they are copied out only with `tags`."""
+    """Plan family ranges through the kernels (run_batches), each materialized into the engine's
+    staging images just before it uploads: the host builds range i + 1 while the kernels of range
+    i run.  `timing` also gets the seconds of materialize."""
     import time
     T = timing if timing is not None else {}
-    parts: List[Consensus] = []
-    prev = None
 
-    def out(fb, db):
-        t0 = time.perf_counter()
-        o = db.fetch(ss=tags)
-        t1 = time.perf_counter()
-        parts.append(consensus_from_output(fb, o))
-        T["fetch"] = T.get("fetch", 0.0) + t1 - t0
-        T["unpack"] = T.get("unpack", 0.0) + time.perf_counter() - t1
-    for a, b in ranges:
-        t0 = time.perf_counter()
-        fb = materialize(plan, a, b, images=engine.stage_images)
-        t1 = time.perf_counter()
-        db = engine.upload(fb, tags=tags, filt=filter is not None)
-        engine.run(db, mode | (MODE_TAGS if db.tags else 0))
-        if filter is not None:
-            engine.filter(db, filter, molecular)
-        T["materialize"] = T.get("materialize", 0.0) + t1 - t0
-        T["upload"] = T.get("upload", 0.0) + time.perf_counter() - t1
-        if prev is not None:
-            out(*prev)
-        prev = (fb, db)
-    if prev is not None:
-        out(*prev)
-    return parts
+    def staged():
+        for a, b in ranges:
+            t0 = time.perf_counter()
+            fb = materialize(plan, a, b, images=engine.stage_images)
+            T["materialize"] = T.get("materialize", 0.0) + time.perf_counter() - t0
+            yield fb
+    return run_batches(engine, staged(), mode, tags, T, filter, molecular)
 
 
 def materialize_ranges(plan: FamilyPlan, ranges, images=None) -> List[FamilyBatch]:
@@ -300,9 +280,11 @@ def materialize_ranges(plan: FamilyPlan, ranges, images=None) -> List[FamilyBatc
 def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
                 timing: Optional[dict] = None, filter: Optional[FilterParams] = None,
                 molecular: bool = False) -> List[Consensus]:
-    """Materialized batches through the kernels, one launch each, output per batch in order; a
-    batch uploads and launches before the one before it is fetched.  `timing`, `filter` and
-    `molecular` as run_ranges."""
+    """Materialized batches (any iterable, taken one at a time) through the kernels, one launch
+    each, output per batch in order; a batch uploads and launches before the one before it is
+    fetched.  `timing`: seconds added per host step (upload, fetch = wait + copy out, unpack).
+    `filter`: each batch is filtered on the device after its vote (Engine.filter; `molecular`:
+    step-1 records), which needs the tags' rows there; they are copied out only with `tags`."""
     import time
     T = timing if timing is not None else {}
     parts: List[Consensus] = []

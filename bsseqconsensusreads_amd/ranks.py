@@ -14,7 +14,7 @@ unclipped 5' end, TemplateCoordinate order) leave gaps.
    that contig, at least 2 * slack on, with no same-contig template key within KEY_GUARD positions
    (a family's keys lie within the tools' jitter of each other, so none straddles x).  It also
    returns where the records at x - slack and at x + slack start.  That reads a few MB per cut.
-2. Rank r owns the keys [X_r, X_r+1).  It runs the one-GPU streaming step (bam._stream_step:
+2. Rank r owns the keys [X_r, X_r+1).  It runs the one-GPU streaming step (stream.run:
    decode, plan, GPU, records, BGZF) over the window from the record at X_r - slack to the one
    at X_r+1 + slack (windows overlap by 2 * slack) and keeps only the records it owns
    (bsdc_bam_stream_set_owner): a template's records near a boundary are read by both ranks and
@@ -28,9 +28,9 @@ unclipped 5' end, TemplateCoordinate order) leave gaps.
    and the owner cuts its output into pieces at every deferred key (and defers the families that
    may interleave with one).  No record is then foreign to every window.  Phase 2: the parent joins
    the spills into one BAM in file order, and one rank runs the stream over it, cut at the union
-   of the deferred keys (bam._stream_step late_splices).
+   of the deferred keys (stream.StreamJob late_splices).
 4. The parent assembles the pieces of every rank and of phase 2 in key order, then one BGZF EOF
-   block (bam.assemble).  The BAM and the FASTQ pair decompress to the one-process stream's bytes
+   block (stream.assemble).  The BAM and the FASTQ pair decompress to the one-process stream's bytes
    (tests/test_ranks.py, with mates on a second contig, unmapped mates and long inserts); only the
    BGZF block boundaries at the seams differ.
 5. With deferral off (defer=0) a template whose insert is longer than slack would have its far
@@ -48,6 +48,7 @@ already run; the GPU stage takes the engine when it has its first batches.
 """
 from __future__ import annotations
 
+import dataclasses
 import multiprocessing as mp
 import os
 import threading
@@ -83,22 +84,17 @@ def windows_of(cuts) -> List[Tuple[int, int, int, int]]:
     return [(lo[r][0], lo[r][1], hi[r][0], hi[r][1]) for r in range(len(cuts) + 1)]
 
 
-def _run_job(r: int, eng, runner, job: dict) -> tuple:
-    """One rank's part of the file: the one-GPU stream over its window, its own keys only -- or the
-    spill's pass (job["late"]: the deferred keys to cut at)."""
-    from . import bam
+def _run_job(r: int, eng, runner, job) -> tuple:
+    """One rank's part of the file (job: a stream.StreamJob): the one-GPU stream over its window,
+    its own keys only -- or the spill's pass (job.late_splices: the deferred keys to cut at)."""
+    from . import stream
     st, rs = {}, {}
     t0 = time.perf_counter()
     marks: list = []
+    if runner is not None:  # (a stand-in runner deflates on the host)
+        job = dataclasses.replace(job, gpu_bgzf=False)
     try:
-        info = bam._stream_step(job["in_bam"], job["fasta"], job["out_bam"], eng, job["prefix"], job["threads"],
-                                job["level"], job["fastq"], job["tags"], job["chunk_bytes"], job["slack"],
-                                job["batch_bases"], st, job["gpu_bgzf"] and runner is None, None, rng=job["rng"],
-                                fragment=job["fragment"], runner=runner, range_stats=rs,
-                                owner=(r, job["cuts"], job["flags"]) if job["cuts"] else None, spill=job["spill"],
-                                marks=marks, defer=job["defer"], late_splices=job.get("late"),
-                                first_key=job.get("first_key"), read_size=job.get("read_size", 8 << 20),
-                                regions=True)
+        info = stream.run(job, eng, runner, st, rs, marks)
     except OSError as e:
         if "foreign record" in str(e):
             return ("foreign", r, str(e))
@@ -183,7 +179,7 @@ def _rank_server(i: int, device: int, runner_spec: Optional[str], tq, rq):
             if job is None:
                 break
             try:
-                rq.put(_run_job(job["rank"], eng, runner, job) + (job["call"],))
+                rq.put(_run_job(job["rank"], eng, runner, job["job"]) + (job["call"],))
             except BaseException as e:  # noqa: BLE001 -- reported to the parent, which raises it
                 rq.put(("error", job["rank"], "%s: %s\n%s" % (type(e).__name__, e, traceback.format_exc()), job["call"]))
     except BaseException as e:  # noqa: BLE001
@@ -236,8 +232,8 @@ class RankPool:
                     self.broken = True
                     raise RuntimeError("rank %d exited (code %s)" % (dead[0], self.procs[dead[0]].exitcode))
 
-    def run(self, jobs: Sequence[dict]) -> list:
-        """Jobs 0..k-1 on ranks 0..k-1 (k <= n); their results in order.  A failing or foreign
+    def run(self, jobs: Sequence) -> list:
+        """Jobs (stream.StreamJob) 0..k-1 on ranks 0..k-1 (k <= n); their results in order.  A failing or foreign
         rank raises after every rank has answered (the pool stays usable); replies of an earlier
         call (its ranks answered after it raised) are dropped by their call id."""
         if self.broken:
@@ -245,7 +241,7 @@ class RankPool:
         self.calls += 1
         call = self.calls
         for r, job in enumerate(jobs):
-            self.tqs[r].put(dict(job, rank=r, call=call))
+            self.tqs[r].put({"job": job, "rank": r, "call": call})
         res, bad = {}, None
         while len(res) < len(jobs):
             m = self.get()
@@ -305,7 +301,7 @@ def step5_ranks(in_bam: str, fasta: str, out_bam: Optional[str], devices: Sequen
 
     import numpy as np
 
-    from . import bam
+    from . import bam, stream
     if out_bam is None and fastq is None:
         raise ValueError("step5_ranks: no output (out_bam and fastq are both None)")
     chunk_bytes = bam.DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes
@@ -335,16 +331,19 @@ def step5_ranks(in_bam: str, fasta: str, out_bam: Optional[str], devices: Sequen
                     os.unlink(path)
 
     def first_key(r, cuts):  # the sort key of rank r's first piece (its lower boundary's)
-        return (bam.MINKEY, 0, 1) if r == 0 else (cuts[r - 1]["key"][0], cuts[r - 1]["key"][1], 1)
+        return (stream.MINKEY, 0, 1) if r == 0 else (cuts[r - 1]["key"][0], cuts[r - 1]["key"][1], 1)
+
+    # what every rank's job shares
+    base = stream.StreamJob(in_bam, fasta, None, prefix=pre, threads=threads, level=level, tags=tags,
+                            gpu_bgzf=gpu_bgzf, chunk_bytes=chunk_bytes, slack=slack,
+                            batch_bases=batch_bases, read_size=read_size, regions=True)
 
     def run(cuts, pl: "RankPool", ranges, t: str, dsp: int):
         n = len(ranges)
         fr = paths(t, n, dsp > 0)
-        jobs = [dict(in_bam=in_bam, fasta=fasta, out_bam=fr[r]["bam"], prefix=pre, threads=threads, level=level,
-                     fastq=fr[r]["fq"], tags=tags, chunk_bytes=chunk_bytes, slack=slack, batch_bases=batch_bases,
-                     gpu_bgzf=gpu_bgzf, rng=ranges[r], cuts=cuts, flags=bam.OWN_STOP_FOREIGN, spill=fr[r]["spill"],
-                     fragment="first" if r == 0 else "next", defer=dsp, first_key=first_key(r, cuts),
-                     read_size=read_size)
+        jobs = [dataclasses.replace(base, out_bam=fr[r]["bam"], fastq=fr[r]["fq"], rng=ranges[r],
+                                    owner=(r, cuts, bam.OWN_STOP_FOREIGN) if cuts else None, spill=fr[r]["spill"],
+                                    fragment="first" if r == 0 else "next", defer=dsp, first_key=first_key(r, cuts))
                 for r in range(n)]
         try:
             return pl.run(jobs), fr
@@ -383,12 +382,10 @@ def step5_ranks(in_bam: str, fasta: str, out_bam: Optional[str], devices: Sequen
         if spilled or splices:
             late = np.unique(np.concatenate(splices), axis=0) if splices else np.zeros((0, 2), np.int64)
             spill_bam = os.path.join(tmpdir, ".%s.spill.bam" % tag)
-            n_def = bam.write_spill_bam(spill_bam, hdr, [f["spill"] for f in frags], 1, threads)
+            n_def = stream.write_spill_bam(spill_bam, hdr, [f["spill"] for f in frags], 1, threads)
             fr2 = paths(tag + "x", 1, False)
-            job = dict(in_bam=spill_bam, fasta=fasta, out_bam=fr2[0]["bam"], prefix=pre, threads=threads, level=level,
-                       fastq=fr2[0]["fq"], tags=tags, chunk_bytes=chunk_bytes, slack=slack, batch_bases=batch_bases,
-                       gpu_bgzf=gpu_bgzf, rng=None, cuts=[], flags=0, spill=None, fragment="next", defer=0,
-                       late=late, read_size=read_size)
+            job = dataclasses.replace(base, in_bam=spill_bam, out_bam=fr2[0]["bam"], fastq=fr2[0]["fq"],
+                                      fragment="next", defer=0, late_splices=late)
             try:
                 phase2 = pool.run([job])
             except BaseException:
@@ -399,11 +396,11 @@ def step5_ranks(in_bam: str, fasta: str, out_bam: Optional[str], devices: Sequen
         for ph, (res, fr) in enumerate(((results, frags), (phase2, fr2))):
             for r, (inf, _, _) in enumerate(res):
                 f = fr[r]
-                pieces += bam.pieces_of(inf["marks"], [f["bam"]] + (list(f["fq"]) if f["fq"] else [None, None]), ph, r)
+                pieces += stream.pieces_of(inf["marks"], [f["bam"]] + (list(f["fq"]) if f["fq"] else [None, None]), ph, r)
         dsts = [out_bam, fastq[0] if fastq else None, fastq[1] if fastq else None]
         for k in range(3):
             if dsts[k] is not None:
-                bam.assemble(dsts[k], pieces, k)
+                stream.assemble(dsts[k], pieces, k)
         t3 = time.perf_counter()
     except BaseException:
         if own:

@@ -127,17 +127,19 @@ class _Engine:
 def standin(monkeypatch):
     monkeypatch.setattr(device, "PinnedPool", _HostPool)
     orig = pipeline.materialize_ranges
+    raw_of = {}  # id(batch) -> the chunk's records
 
     def materialize_ranges(plan, ranges, images=None):
         fbs = orig(plan, ranges, images)
-        for fb in fbs:
-            fb._raw = plan.raw
+        raw_of.update((id(fb), plan.raw) for fb in fbs)
         return fbs
 
-    def run_batches(engine, batches, mode, tags=False, timing=None):
+    def run_batches(engine, batches, mode, tags=False, timing=None, filter=None, molecular=False):
         assert mode == pipeline.MODE_VOTE
-        return [pipeline.consensus_from_output(fb, engine.runner.run_batch(fb, mode, tags, R.take(fb._raw, np.asarray(
-            fb.src, np.int64)))) for fb in batches]
+        if filter is not None:
+            raise NotImplementedError("the oracle stand-in cannot filter")
+        return [pipeline.consensus_from_output(fb, engine.runner.run_batch(fb, mode, tags, R.take(
+            raw_of.pop(id(fb)), np.asarray(fb.src, np.int64)))) for fb in batches]
     monkeypatch.setattr(pipeline, "materialize_ranges", materialize_ranges)
     monkeypatch.setattr(pipeline, "run_batches", run_batches)
     return _Engine()
