@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # BSDC_LIB_PATH: an alternative build of the same library (profiling A/B runs only)
 LIB_PATH = os.environ.get("BSDC_LIB_PATH") or os.path.join(HERE, "libbsdc.so")
 
-BSDC_ABI_VERSION = 16
+BSDC_ABI_VERSION = 17
 SMALL_BUCKETS = 8  # BSDC_SMALL_BUCKETS
 LARGE_BUCKETS = 6  # BSDC_LARGE_BUCKETS
 MODE_CONVERT, MODE_EXTEND, MODE_VOTE, MODE_DUMP = 1, 2, 4, 8
@@ -28,6 +28,15 @@ class FilterParamsC(C.Structure):
                 ("max_base_error_rate", C.c_double * 3), ("min_base_quality", C.c_int32),
                 ("max_no_call_fraction", C.c_double), ("min_mean_base_quality", C.c_int32),
                 ("require_single_strand_agreement", C.c_int32)]
+
+
+class InflateBlockC(C.Structure):  # bsdc_inflate_block
+    _fields_ = [("src", C.c_int64), ("clen", C.c_int32), ("isize", C.c_int32), ("dst", C.c_int64)]
+
+
+# bsdc_bgzf_inflate's status codes (BSDC_INFLATE_E*)
+(INFLATE_EBTYPE, INFLATE_ESTORED, INFLATE_ELENGTHS, INFLATE_EREPEAT, INFLATE_ESYMBOL, INFLATE_EDIST, INFLATE_EOVERFLOW,
+ INFLATE_ESHORT, INFLATE_EINPUT, INFLATE_ECOUNTS, INFLATE_ENOEOB, INFLATE_ECODE, INFLATE_ERANGE) = range(1, 14)
 
 
 class FamilyBatchC(C.Structure):
@@ -56,7 +65,8 @@ EXPORTS = ("bsdc_abi_version", "bsdc_ctx_create", "bsdc_ctx_set_params", "bsdc_c
            "bsdc_load_reference", "bsdc_run", "bsdc_convert", "bsdc_extend", "bsdc_duplex_call",
            "bsdc_family_arena_bytes", "bsdc_small_arena_bytes", "bsdc_get_tables", "bsdc_model_tables",
            "bsdc_model_tables_fp64", "bsdc_agree_tables", "bsdc_phred_buckets", "bsdc_bgzf_scratch_bytes",
-           "bsdc_bgzf_deflate", "bsdc_bgzf_pack", "bsdc_host_register", "bsdc_host_unregister", "bsdc_filter")
+           "bsdc_bgzf_deflate", "bsdc_bgzf_pack", "bsdc_host_register", "bsdc_host_unregister", "bsdc_filter",
+           "bsdc_bgzf_inflate", "bsdc_bgzf_inflate_host")
 
 _lib = None
 
@@ -114,6 +124,11 @@ def load(path: str = LIB_PATH):
     lib.bsdc_filter.argtypes = [C.c_void_p, C.POINTER(FilterParamsC), C.c_int32, C.c_int64, C.POINTER(ConsensusC),
                                 C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bsdc_filter.restype = C.c_int32
+    lib.bsdc_bgzf_inflate.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                      C.c_void_p]
+    lib.bsdc_bgzf_inflate.restype = C.c_int32
+    lib.bsdc_bgzf_inflate_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.bsdc_bgzf_inflate_host.restype = C.c_int32
     if lib.bsdc_abi_version() != BSDC_ABI_VERSION:
         raise RuntimeError("libbsdc ABI %d != %d" % (lib.bsdc_abi_version(), BSDC_ABI_VERSION))
     if path == LIB_PATH:

@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import time
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
@@ -31,8 +32,10 @@ from . import records as R
 
 IO_LIB_PATH = os.environ.get("BSDC_IO_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)),
                                                                  "libbsdc_io.so")
-BSDC_IO_ABI_VERSION = 12
+BSDC_IO_ABI_VERSION = 13
 _P = C.c_void_p
+# bsdc_inflate_fn (include/bsdc_io.h): user, comp, n_comp, blk, nblk, out, n_out -> 0 or an error
+INFLATE_FN = C.CFUNCTYPE(C.c_int32, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64)
 
 
 class _Sizes(C.Structure):
@@ -146,6 +149,8 @@ def _load():
     lib.bsdc_bam_stream_spill.restype = C.c_int64
     lib.bsdc_bam_stream_set_defer.argtypes = [_P, C.c_int64]
     lib.bsdc_bam_stream_set_defer.restype = C.c_int32
+    lib.bsdc_bam_stream_set_inflater.argtypes = [_P, INFLATE_FN, _P]
+    lib.bsdc_bam_stream_set_inflater.restype = C.c_int32
     lib.bsdc_bam_stream_splices.argtypes = [_P, _P]
     lib.bsdc_bam_stream_splices.restype = C.c_int64
     lib.bsdc_bam_rec_keys.argtypes = [_P, _P]
@@ -457,7 +462,7 @@ def spill_sorted_records(data: bytes):
 
 def stream_chunks(path: str, threads: int = 0, chunk_bytes: int = DEFAULT_CHUNK_BYTES, slack: int = DEFAULT_SLACK,
                   read_size: int = 8 << 20, runs: bool = False, rng=None, stats: Optional[dict] = None, owner=None,
-                  defer: int = 0, keys: bool = False):
+                  defer: int = 0, keys: bool = False, inflater=None):
     """The chunks of a coordinate-sorted BAM in bounded memory, undecoded (StreamChunk): cut where no
     template or MI family straddles two chunks (include/bsdc_io.h, bsdc_bam_stream_next_raw).  The
     stream itself is freed once it is exhausted and every chunk has been decoded or discarded.
@@ -473,9 +478,12 @@ def stream_chunks(path: str, threads: int = 0, chunk_bytes: int = DEFAULT_CHUNK_
     chunk then carries its `spill` entries and its `splices` (the deferred keys its output is cut
     before), and its records decode with their keys (RawRecords.tc_key); once exhausted, `stats`
     receives the rest as "spill_tail" and "splices_tail".  keys: the records decode with their keys
-    in any case."""
+    in any case.  inflater: the blocks' inflate goes to it (bsdc_bam_stream_set_inflater): a
+    GpuInflate, or any object whose `callback` is an INFLATE_FN (kept alive here for the stream's
+    lifetime); the chunks are the same bytes."""
     lib = _load()
     st = _P()
+    hook = None if inflater is None else inflater.callback  # (referenced until the stream is closed)
     if rng is None:
         rc = lib.bsdc_bam_stream_open(path.encode(), int(threads), int(read_size), C.byref(st))
     else:
@@ -484,6 +492,8 @@ def stream_chunks(path: str, threads: int = 0, chunk_bytes: int = DEFAULT_CHUNK_
     if rc != 0:
         raise OSError("%s: %s" % (path, lib.bsdc_io_last_error().decode()))
     try:
+        if hook is not None and lib.bsdc_bam_stream_set_inflater(st, hook, None) != 0:
+            raise OSError("%s: %s" % (path, lib.bsdc_io_last_error().decode()))
         if owner is not None:
             rank, cuts = owner[:2]
             flags = int(owner[2]) if len(owner) > 2 else 0  # OWN_* (True: OWN_STOP_FOREIGN)
@@ -521,11 +531,11 @@ def stream_chunks(path: str, threads: int = 0, chunk_bytes: int = DEFAULT_CHUNK_
 
 
 def stream_bam(path: str, threads: int = 0, chunk_bytes: int = DEFAULT_CHUNK_BYTES, slack: int = DEFAULT_SLACK,
-               read_size: int = 8 << 20):
+               read_size: int = 8 << 20, inflater=None):
     """Chunks of a coordinate-sorted BAM in bounded memory: yields (BamHeader, RawRecords) per chunk,
     cut where no template or MI family straddles two chunks (include/bsdc_io.h,
-    bsdc_bam_stream_next); names and MI ids are chunk-local."""
-    for c in stream_chunks(path, threads, chunk_bytes, slack, read_size):
+    bsdc_bam_stream_next); names and MI ids are chunk-local.  inflater: as stream_chunks'."""
+    for c in stream_chunks(path, threads, chunk_bytes, slack, read_size, inflater=inflater):
         yield c.decode(threads)
 
 
@@ -879,6 +889,81 @@ class GpuBgzf:
         self.submit(raw, nblk)
         packed, sizes = self.finish()
         return packed[:int(np.maximum(sizes, 0).sum())].copy(), sizes
+
+
+class GpuInflate:
+    """Inflate of the input BAM's BGZF blocks on one GPU (libbsdc bsdc_bgzf_inflate,
+    csrc/bsdc_inflate.hip), as the streaming reader's inflater (stream_chunks(inflater=...),
+    bsdc_bam_stream_set_inflater): per fill one call -- the compressed bytes and the block table go
+    to HBM through pinned staging, one workgroup inflates each block, the bytes and the blocks'
+    status come back, the stream is synchronised.  Non-zero when any block's status is (the reader
+    then fails with its corrupt-BGZF error); the reader checks every block's CRC32 itself.  Its own
+    HIP stream, so a fill overlaps the consensus kernels.  Counters: fills, blocks, bytes_in
+    (compressed), bytes_out, seconds (inside the calls)."""
+
+    def __init__(self, device):
+        import torch
+
+        from . import _lib
+        self.torch = torch
+        self._lib = _lib
+        self.lib = _lib.load()
+        self.dev = torch.device(device)
+        self.stream = torch.cuda.Stream(self.dev)
+        self.buf = {}  # grown on demand: device comp / out / blk / status, pinned comp_h / out_h / blk_h / status_h
+        self.fills = self.blocks = self.bytes_in = self.bytes_out = 0
+        self.seconds = 0.0
+        self.error = None  # the exception of a failed call (the reader reports a corrupt block)
+        self.callback = INFLATE_FN(self._call)
+
+    _buf = GpuBgzf._buf
+
+    def inflate(self, comp: np.ndarray, blk: np.ndarray, n_out: int):
+        """comp: uint8 host bytes; blk: the block table as a uint8 view of nblk x 24 bytes
+        (bsdc_inflate_block) -> (out: a pinned uint8 view of n_out bytes, valid until the next call,
+        status int32[nblk])."""
+        torch = self.torch
+        nblk, n_comp = blk.shape[0] // 24, comp.shape[0]
+        d_comp, h_comp = self._buf("comp", n_comp), self._buf("comp_h", n_comp, pinned=True)
+        d_blk, h_blk = self._buf("blk", nblk * 24), self._buf("blk_h", nblk * 24, pinned=True)
+        d_out, h_out = self._buf("out", n_out), self._buf("out_h", n_out, pinned=True)
+        d_st = self._buf("status", nblk, torch.int32)
+        h_st = self._buf("status_h", nblk, torch.int32, pinned=True)
+        h_comp.numpy()[:n_comp] = comp
+        h_blk.numpy()[:nblk * 24] = blk
+        with torch.cuda.stream(self.stream):
+            d_comp[:n_comp].copy_(h_comp[:n_comp], non_blocking=True)
+            d_blk[:nblk * 24].copy_(h_blk[:nblk * 24], non_blocking=True)
+            if self.lib.bsdc_bgzf_inflate(d_comp.data_ptr(), n_comp, d_blk.data_ptr(), nblk, d_out.data_ptr(), n_out,
+                                          d_st.data_ptr(), self.stream.cuda_stream) != 0:
+                raise RuntimeError("bsdc_bgzf_inflate failed")
+            h_st[:nblk].copy_(d_st[:nblk], non_blocking=True)
+            h_out[:n_out].copy_(d_out[:n_out], non_blocking=True)
+        self.stream.synchronize()
+        return h_out.numpy()[:n_out], h_st.numpy()[:nblk]
+
+    def _call(self, user, comp, n_comp, blk, nblk, out, n_out) -> int:
+        t0 = time.perf_counter()
+        try:
+            as_u8 = lambda p, n: np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(int(n),))  # noqa: E731
+            got, status = self.inflate(as_u8(comp, n_comp), as_u8(blk, 24 * nblk), int(n_out))
+            bad = bool(status.any())
+            if not bad:
+                as_u8(out, n_out)[:] = got
+            self.fills += 1
+            self.blocks += int(nblk)
+            self.bytes_in += int(n_comp)
+            self.bytes_out += int(n_out)
+            return 1 if bad else 0
+        except BaseException as e:  # noqa: BLE001 -- nothing may unwind through the C caller
+            self.error = e
+            return -1
+        finally:
+            self.seconds += time.perf_counter() - t0
+
+    def counters(self) -> dict:
+        return {"fills": self.fills, "blocks": self.blocks, "bytes_in": self.bytes_in, "bytes_out": self.bytes_out,
+                "seconds": round(self.seconds, 4)}
 
 
 class BamWriter:

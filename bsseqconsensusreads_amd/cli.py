@@ -55,6 +55,8 @@ def parse(argv):
         p.add_argument("--device", type=int, default=0)
         p.add_argument("--gpu-bgzf", default="false", choices=("true", "false"),
                        help="deflate the output BAM's and FASTQ pair's blocks on the GPU (streaming; files ~4%% larger)")
+        p.add_argument("--gpu-inflate", default="false", choices=("true", "false"),
+                       help="inflate the input BAM's BGZF blocks on the GPU (streaming, --gpus 1; the same output)")
         p.add_argument("--batch-bases", type=int, default=None, help="device batch budget in bases")
         p.add_argument("--chunk-mb", type=int, default=64, help="--stream: record MiB per chunk")
         if name == "step5":
@@ -104,6 +106,11 @@ def parse(argv):
         ap.error("--fastq1 and --fastq2 go together")
     if a.output == "-" and a.fastq1 is None:
         ap.error("nothing to write: give OUT.bam or --fastq1/--fastq2")
+    if a.gpu_inflate == "true" and getattr(a, "gpus", 1) > 1:
+        ap.error("--gpu-inflate is not supported with --gpus %d yet (the rank processes start without torch)" % a.gpus)
+    if a.gpu_inflate == "true" and a.stream == "false":
+        print("warning: --gpu-inflate applies to the streaming step only; --stream false inflates on the host",
+              file=sys.stderr)
     if a.gpu_bgzf == "true" and a.stream == "false":
         print("warning: --gpu-bgzf applies to the streaming step only; --stream false deflates on the host",
               file=sys.stderr)
@@ -200,7 +207,8 @@ def main(argv=None) -> int:
             if stream:
                 info = bam.step5_stream(a.input, a.reference, out, eng, a.read_name_prefix, a.threads, a.compression,
                                         fq, tags=a.output_per_base_tags == "true", chunk_bytes=a.chunk_mb << 20,
-                                        batch_bases=a.batch_bases, gpu_bgzf=a.gpu_bgzf == "true", filter=flt)
+                                        batch_bases=a.batch_bases, gpu_bgzf=a.gpu_bgzf == "true", filter=flt,
+                                        gpu_inflate=a.gpu_inflate == "true")
             elif a.cmd == "step5":
                 info = bam.step5(a.input, a.reference, out, eng, a.read_name_prefix, a.threads, a.compression, fq,
                                  tags=a.output_per_base_tags == "true", batch_bases=a.batch_bases, dist=dist,
@@ -209,7 +217,8 @@ def main(argv=None) -> int:
                 info = bam.molecular_stream(a.input, out, eng, a.read_name_prefix, a.threads, a.compression, fq,
                                             tags=a.output_per_base_tags == "true", chunk_bytes=a.chunk_mb << 20,
                                             batch_bases=a.batch_bases, gpu_bgzf=a.gpu_bgzf == "true",
-                                            min_consensus_base_quality=a.min_consensus_base_quality, filter=flt)
+                                            min_consensus_base_quality=a.min_consensus_base_quality, filter=flt,
+                                            gpu_inflate=a.gpu_inflate == "true")
             else:
                 info = bam.molecular(a.input, out, eng, a.read_name_prefix, a.threads, a.compression, fq,
                                      tags=a.output_per_base_tags == "true",

@@ -365,9 +365,13 @@ namespace {
 // Whole BGZF blocks of comp[0, n) inflated (in parallel) and appended to `out`; *used = the bytes
 // of the whole blocks (a trailing partial block is left for the caller unless `final`, where it
 // is an error).  Every block is CRC-checked.
-int32_t inflate_blocks(const uint8_t *comp, int64_t n, bool final, Bytes &out, int64_t *used) {
+// With an inflater (bsdc_bam_stream_set_inflater) the blocks with bytes go to it in one call in place
+// of the inflate loop; the CRC32 check of its bytes stays here.
+int32_t inflate_blocks(const uint8_t *comp, int64_t n, bool final, Bytes &out, int64_t *used,
+                       bsdc_inflate_fn inflater = nullptr, void *inflater_user = nullptr) {
     std::vector<int64_t> boff, bsz, uoff;
-    int64_t o = 0, u = (int64_t)out.size();
+    const int64_t u0 = (int64_t)out.size();
+    int64_t o = 0, u = u0;
     *used = 0;
     while (o < n) {
         const uint8_t *h = comp + o;
@@ -405,6 +409,35 @@ int32_t inflate_blocks(const uint8_t *comp, int64_t n, bool final, Bytes &out, i
     out.resize((size_t)u);
     const int64_t nb = (int64_t)boff.size();
     int bad = 0;
+    if (inflater) {
+        std::vector<bsdc_inflate_block> d;
+        d.reserve((size_t)nb);
+        for (int64_t i = 0; i < nb; i++) {
+            const uint8_t *h = comp + boff[i];
+            const int xlen = rd16(h + 10);
+            const int64_t clen = bsz[i] - 12 - xlen - 8;
+            const uint32_t isize = rd32(h + bsz[i] - 4);
+            if (isize == 0) continue;
+            if (clen < 0 || isize > 65536) {
+                bad |= 1;
+                break;
+            }
+            d.push_back(bsdc_inflate_block{boff[i] + 12 + xlen, (int32_t)clen, (int32_t)isize, uoff[i] - u0});
+        }
+        if (!bad && !d.empty() && inflater(inflater_user, comp, o, d.data(), (int64_t)d.size(), out.data() + u0, u - u0) != 0)
+            bad |= 1;
+        if (!bad) {
+#pragma omp parallel for schedule(dynamic, 16) reduction(| : bad)
+            for (int64_t i = 0; i < nb; i++) {
+                const uint8_t *h = comp + boff[i];
+                const uint32_t isize = rd32(h + bsz[i] - 4), crc = rd32(h + bsz[i] - 8);
+                if (isize && crc32_of(out.data() + uoff[i], isize) != crc) bad |= 1;
+            }
+        }
+        if (bad) return fail(BSDC_IO_EFORMAT, "corrupt BGZF block (inflate or CRC32)");
+        *used = o;
+        return 0;
+    }
 #pragma omp parallel for schedule(dynamic, 16) reduction(| : bad)
     for (int64_t i = 0; i < nb; i++) {
         const uint8_t *h = comp + boff[i];
@@ -734,6 +767,11 @@ struct bsdc_bam_stream {
     // last block's drop_tail bytes; fpos = the file offset read so far
     int64_t fpos = 0, limit = -1, skip_head = 0, drop_tail = 0;
     int64_t hdr_len = 0;  // the header's uncompressed bytes (the first record's offset)
+    // (bsdc_bam_stream_set_inflater) the blocks' inflate handed to the caller; where the records
+    // start (file offset of the block, bytes to skip in it), for the rewind that setting it does
+    bsdc_inflate_fn inflater = nullptr;
+    void *inflater_user = nullptr;
+    int64_t start_pos = 0, start_skip = 0;
     // a rank's key interval (bsdc_bam_stream_set_owner): -1 = every record
     int32_t own_rank = -1;
     std::vector<TcKey> own_bounds;
@@ -777,6 +815,7 @@ int32_t bsdc_bam_stream_open(const char *path, int32_t n_threads, int64_t read_s
             s->buf.erase(s->buf.begin(), s->buf.begin() + p);
             s->tail = 0;
             s->hdr_len = p;
+            s->start_skip = p;
             break;
         }
         if (s->eof) {
@@ -833,6 +872,8 @@ int32_t bsdc_bam_stream_open_range(const char *path, int32_t n_threads, int64_t 
         s->eof = false;
         s->fpos = start_block;
         s->skip_head = start_off;
+        s->start_pos = start_block;
+        s->start_skip = start_off;
     }
     if (end_block >= 0) {
         if (start_block >= 0 ? end_block < start_block : false) {
@@ -873,6 +914,26 @@ void bsdc_bam_stream_range_stats(const bsdc_bam_stream *s, int64_t *st) {
     st[4] = s->st_spilled;
     st[5] = s->st_deferred;
     st[6] = s->st_peak;
+}
+
+// The inflate of every block from here on goes to fn (include/bsdc_io.h).  Set before the first
+// chunk: the stream goes back to its first record's block (what opening it inflated for the header
+// is dropped), so fn sees every block of the records -- a range stream is there already.
+int32_t bsdc_bam_stream_set_inflater(bsdc_bam_stream *s, bsdc_inflate_fn fn, void *user) {
+    if (!s) return fail(BSDC_IO_EINVAL, "no stream");
+    if (s->seq != 0 || !s->recs.empty() || s->tail != 0 || s->outstanding != 0)
+        return fail(BSDC_IO_EINVAL, "set the inflater before the first chunk");
+    if (fn && (s->fpos != s->start_pos || !s->buf.empty() || !s->comp.empty())) {
+        if (fseeko(s->f, (off_t)s->start_pos, SEEK_SET) != 0) return fail(BSDC_IO_EIO, "seek failed");
+        s->comp.clear();
+        s->buf.clear();
+        s->eof = false;
+        s->fpos = s->start_pos;
+        s->skip_head = s->start_skip;
+    }
+    s->inflater = fn;
+    s->inflater_user = user;
+    return 0;
 }
 
 int32_t bsdc_bam_stream_set_defer(bsdc_bam_stream *s, int64_t span) {
@@ -1178,7 +1239,8 @@ int32_t bsdc_bam_stream_fill(bsdc_bam_stream *s) {
     }
     const size_t before = s->buf.size();
     int64_t used = 0;
-    const int32_t rc = inflate_blocks(s->comp.data(), (int64_t)s->comp.size(), s->eof, s->buf, &used);
+    const int32_t rc = inflate_blocks(s->comp.data(), (int64_t)s->comp.size(), s->eof, s->buf, &used, s->inflater,
+                                      s->inflater_user);
     if (rc != 0) return rc;
     s->comp.erase(s->comp.begin(), s->comp.begin() + used);
     if (s->skip_head > 0 && s->buf.size() > before) {  // a range's first block: the bytes before its first record

@@ -44,7 +44,9 @@ class StreamJob:
     deferred keys the spill's pass cuts at; first_key = the sort key of the rank's first piece;
     regions (the ranks' passes) = also cut before the first family of every new key contig pair (a
     piece keyed (pair, MINKEY)): a rank does not register cross keys (bsdc_io.cpp), so the deferred
-    families of a contig's cross keys go between those pieces."""
+    families of a contig's cross keys go between those pieces.
+    gpu_inflate: the input BAM's BGZF blocks are inflated on the engine's GPU (bam.GpuInflate; the
+    same bytes, so the same output files); an Engine stream only."""
 
     in_bam: str
     fasta: Optional[str]
@@ -69,6 +71,7 @@ class StreamJob:
     late_splices: Optional[np.ndarray] = None
     first_key: Optional[tuple] = None
     regions: bool = False
+    gpu_inflate: bool = False
 
 
 @dataclasses.dataclass
@@ -375,12 +378,12 @@ def step5_stream(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, p
                  threads: int = 0, level: int = 6, fastq: Optional[Tuple[str, str]] = None, tags: bool = True,
                  chunk_bytes: int = bam.DEFAULT_CHUNK_BYTES, slack: int = bam.DEFAULT_SLACK,
                  batch_bases: Optional[int] = None, stats: Optional[dict] = None, gpu_bgzf: bool = False,
-                 defer: Optional[int] = None, read_size: int = 8 << 20, filter=None) -> dict:
+                 defer: Optional[int] = None, read_size: int = 8 << 20, filter=None, gpu_inflate: bool = False) -> dict:
     """step5 in bounded memory, pipelined (run); defer: the span past which a template is
     deferred (default DEFAULT_DEFER_SPAN; 0 = off); read_size: compressed bytes per refill;
-    filter: as step5's."""
+    filter: as step5's; gpu_inflate: the input's BGZF blocks inflate on the GPU (bam.GpuInflate)."""
     job = StreamJob(in_bam, fasta, out_bam, fastq, prefix, threads, level, tags, gpu_bgzf, chunk_bytes, slack,
-                    batch_bases, read_size, filter=filter, defer=defer)
+                    batch_bases, read_size, filter=filter, defer=defer, gpu_inflate=gpu_inflate)
     return _public(run(job, engine, stats=stats))
 
 
@@ -388,7 +391,7 @@ def molecular_stream(in_bam: str, out_bam: Optional[str], engine=None, prefix: O
                      level: int = 6, fastq: Optional[Tuple[str, str]] = None, tags: bool = True,
                      chunk_bytes: int = bam.DEFAULT_CHUNK_BYTES, batch_bases: Optional[int] = None,
                      stats: Optional[dict] = None, gpu_bgzf: bool = False, min_consensus_base_quality: int = 0,
-                     filter=None) -> dict:
+                     filter=None, gpu_inflate: bool = False) -> dict:
     """Rule call_consensus_reads_molecular (main.snake.py:46-55) in bounded memory: the same
     pipeline as step5_stream over a GroupReadsByUmi-ordered input cut between MI runs
     (stream_chunks(runs=True)); each chunk's runs are its consensus families (pipeline.molecular_records,
@@ -396,7 +399,8 @@ def molecular_stream(in_bam: str, out_bam: Optional[str], engine=None, prefix: O
     molecular()'s whole-file path: no run straddles two chunks.  The reference's rule needs -Xmx100g
     (main.snake.py:54, README.md:83); this holds about six chunks."""
     job = StreamJob(in_bam, None, out_bam, fastq, prefix, threads, level, tags, gpu_bgzf, chunk_bytes,
-                    batch_bases=batch_bases, molecular=int(min_consensus_base_quality), filter=filter)
+                    batch_bases=batch_bases, molecular=int(min_consensus_base_quality), filter=filter,
+                    gpu_inflate=gpu_inflate)
     return _public(run(job, engine, stats=stats))
 
 
@@ -552,8 +556,8 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
         eng = Engine(0) if own else engine
     else:
         eng = None
-        if job.gpu_bgzf or molecular or job.filter is not None:
-            raise ValueError("a runner stream: step 5 with host deflate only, unfiltered")
+        if job.gpu_bgzf or molecular or job.filter is not None or job.gpu_inflate:
+            raise ValueError("a runner stream: step 5 with host inflate and deflate only, unfiltered")
     out_bam, fastq = job.out_bam, job.fastq
     info = {"records_in": 0, "families": 0, "families_emitted": 0, "records_out": 0, "chunks": 0,
             "spilled_bytes": 0, "deferred_families": 0, "splices": []}
@@ -588,12 +592,15 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
             eng.close()
         raise
     fault = Fault()
+    inflater = None
     try:
         if ref is not None:
             (runner if runner is not None else eng).load_reference(ref)
+        if job.gpu_inflate:  # (called on the decoder thread, on its own HIP stream)
+            inflater = bam.GpuInflate(eng.device)
         source = dict(path=job.in_bam, threads=job.threads, chunk_bytes=job.chunk_bytes, slack=job.slack,
                       read_size=job.read_size, runs=molecular, rng=job.rng, stats=rs, owner=job.owner, defer=dspan,
-                      keys=late is not None)
+                      keys=late is not None, inflater=inflater)
         front = FrontEnd(fault, source, plan_molecular if molecular else functools.partial(plan_step5, ref=ref),
                          pipeline.materialize_ranges if runner is not None else PinnedBatches(eng), job.threads,
                          job.batch_bases, bufs, spill_path)
@@ -626,6 +633,10 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
                     cuts = sorted(cuts + rc)
                 back.put(cons, ch, cuts)
                 del ch, cons
+        if inflater is not None:
+            info["gpu_inflate"] = inflater.counters()
+            if inflater.error is not None:  # (the reader saw a failed call as a corrupt block)
+                fault.errors.insert(0, inflater.error)
         if not fault.errors:
             info["records_out"] = back.records_out
             info["spilled_bytes"] = front.spilled_bytes
@@ -675,6 +686,8 @@ def _finish_deferred(job: StreamJob, eng, runner, marks, spill_path: str, info: 
                    eng, runner, marks=mk2)
         for k in ("records_in", "families", "families_emitted", "records_out"):
             info[k] += inf2[k]
+        if "gpu_inflate" in inf2:  # (the spill's BAM, inflated the same way)
+            info["gpu_inflate_deferred"] = inf2["gpu_inflate"]
         if job.filter is not None:
             info["filter"] = _filter.add_summary(info["filter"], inf2["filter"])
         pieces = pieces_of(marks, paths, 0, 0) + pieces_of(mk2, p2, 1, 0)

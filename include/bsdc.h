@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BSDC_ABI_VERSION 16
+#define BSDC_ABI_VERSION 17
 #define BSDC_SMALL_BUCKETS 8
 #define BSDC_LARGE_BUCKETS 6
 #define BSDC_LARGE_LDS_MAX 158912 /* LDS arena bytes one large-family workgroup may use */ /* LDS arena size classes of the wavefront-per-family kernel */
@@ -290,6 +290,42 @@ typedef struct {
  * and the ss_* rows are only read.  Device pointers; BSDC_EINVAL when out->ss_* are NULL. */
 int32_t bsdc_filter(bsdc_ctx *ctx, const bsdc_filter_params *params, int32_t kind, int64_t n_fam,
                     bsdc_consensus *out, uint8_t *filt, uint16_t *masked, void *stream);
+
+/* (ABI 17) Inflate of the input BAM's BGZF blocks on the GPU (replaces the inflate of htsjdk's BAM
+ * reader behind CallDuplexConsensusReads --input, main.snake.py:157-163; csrc/bsdc_inflate.hip):
+ * block b's raw DEFLATE data comp[src, src + clen) -> its isize bytes at out + dst, one workgroup
+ * per block; status[b] = 0 when the block inflated to exactly isize bytes, else one of the codes
+ * below and nothing of the block is written.  The input is untrusted: the kernel reads `comp`
+ * only inside [src, src + clen), writes `out` only inside [dst, dst + isize), and ends on any
+ * bytes.  CRC32 / ISIZE stay with the host (libbsdc_io checks the returned
+ * bytes).  bsdc_bgzf_inflate: device pointers, enqueued on `stream` (hipStream_t); returns 0 once
+ * launched.  bsdc_bgzf_inflate_host: host pointers, the same decoding functions run sequentially
+ * on the CPU (no GPU needed) -- the twin the corrupt-input tests run first. */
+typedef struct {
+    int64_t src;    /* offset of the block's raw deflate data in comp */
+    int32_t clen;   /* its bytes */
+    int32_t isize;  /* the bytes it inflates to (BGZF ISIZE, <= 65536) */
+    int64_t dst;    /* offset of the block's bytes in out */
+} bsdc_inflate_block;
+
+#define BSDC_INFLATE_EBTYPE 1     /* block type 3 */
+#define BSDC_INFLATE_ESTORED 2    /* stored block: LEN != ~NLEN */
+#define BSDC_INFLATE_ELENGTHS 3   /* over-subscribed or incomplete code lengths (zlib's rules) */
+#define BSDC_INFLATE_EREPEAT 4    /* repeat code with no previous length, or running past HLIT + HDIST */
+#define BSDC_INFLATE_ESYMBOL 5    /* literal/length symbol 286 / 287 or distance symbol 30 / 31 */
+#define BSDC_INFLATE_EDIST 6      /* distance reaching before the block's start */
+#define BSDC_INFLATE_EOVERFLOW 7  /* output would exceed isize */
+#define BSDC_INFLATE_ESHORT 8     /* final end of block before isize bytes */
+#define BSDC_INFLATE_EINPUT 9     /* the clen bytes are exhausted */
+#define BSDC_INFLATE_ECOUNTS 10   /* HLIT > 286 or HDIST > 30 */
+#define BSDC_INFLATE_ENOEOB 11    /* a dynamic block without an end-of-block code */
+#define BSDC_INFLATE_ECODE 12     /* bits that are no code of an incomplete (or empty) code */
+#define BSDC_INFLATE_ERANGE 13    /* the descriptor leaves comp / out, isize > 65536, or clen > 16 MiB */
+
+int32_t bsdc_bgzf_inflate(const uint8_t *comp, int64_t n_comp, const bsdc_inflate_block *blk, int64_t nblk,
+                          uint8_t *out, int64_t n_out, int32_t *status, void *stream);
+int32_t bsdc_bgzf_inflate_host(const uint8_t *comp, int64_t n_comp, const bsdc_inflate_block *blk, int64_t nblk,
+                               uint8_t *out, int64_t n_out, int32_t *status);
 
 #ifdef __cplusplus
 }

@@ -13,11 +13,13 @@
 #ifndef BSDC_IO_H
 #define BSDC_IO_H
 #include <stdint.h>
+
+#include "bsdc.h" /* bsdc_inflate_block (declarations only: libbsdc_io links nothing of libbsdc) */
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define BSDC_IO_ABI_VERSION 12
+#define BSDC_IO_ABI_VERSION 13
 #define BSDC_IO_EFORMAT (-10) /* not BGZF/BAM, truncated, bad CRC */
 #define BSDC_IO_EIO (-11)     /* open/read/write failed */
 #define BSDC_IO_EINVAL (-22)  /* bad argument */
@@ -170,6 +172,20 @@ void bsdc_bam_stream_range_stats(const bsdc_bam_stream *s, int64_t *st);
  * unmapped or absent), out[2k + 1] = the lower end's unclipped 5' position, from the input's
  * cigar and MC; within 4 positions of the key of the records tools 1 and 2 make. */
 int32_t bsdc_bam_stream_set_defer(bsdc_bam_stream *s, int64_t span);
+/* (IO ABI 13) The stream's inflate handed to the caller (bam.GpuInflate: the GPU, libbsdc
+ * bsdc_bgzf_inflate; replaces the inflate of htsjdk's BAM reader behind CallDuplexConsensusReads
+ * --input, main.snake.py:157-163).  Each fill still scans the block headers itself, then calls fn
+ * once for its blocks with ISIZE > 0 -- comp[0, n_comp) the fill's compressed bytes, blk[b].src the
+ * offset of block b's raw deflate data in them, blk[b].dst the offset of its bytes in out (host
+ * memory, n_out bytes; block 0's dst is 0) -- in place of its own inflate loop, and checks the
+ * CRC32 of every block's bytes afterwards (in parallel).  A non-zero return, or a CRC mismatch,
+ * fails the stream with BSDC_IO_EFORMAT "corrupt BGZF block (inflate or CRC32)".  Set before the
+ * first chunk (BSDC_IO_EINVAL after): the stream returns to its first record's block, so fn sees
+ * every block that holds records (and the header's last one).  fn is called on the thread that
+ * reads the stream; NULL restores the host inflate. */
+typedef int32_t (*bsdc_inflate_fn)(void *user, const uint8_t *comp, int64_t n_comp, const bsdc_inflate_block *blk,
+                                   int64_t nblk, uint8_t *out, int64_t n_out);
+int32_t bsdc_bam_stream_set_inflater(bsdc_bam_stream *s, bsdc_inflate_fn fn, void *user);
 int64_t bsdc_bam_stream_spill(bsdc_bam_stream *s, uint8_t *dst);
 int64_t bsdc_bam_stream_splices(bsdc_bam_stream *s, int64_t *dst);
 int32_t bsdc_bam_rec_keys(const bsdc_bam *b, int64_t *out);
