@@ -32,7 +32,7 @@ from . import records as R
 
 IO_LIB_PATH = os.environ.get("BSDC_IO_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)),
                                                                  "libbsdc_io.so")
-BSDC_IO_ABI_VERSION = 13
+BSDC_IO_ABI_VERSION = 14
 _P = C.c_void_p
 # bsdc_inflate_fn (include/bsdc_io.h): user, comp, n_comp, blk, nblk, out, n_out -> 0 or an error
 INFLATE_FN = C.CFUNCTYPE(C.c_int32, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64)
@@ -90,31 +90,24 @@ def _load():
     lib.bsdc_bam_stream_recycle.restype = None
     lib.bsdc_bam_stream_header.argtypes = [_P, C.POINTER(_P)]
     lib.bsdc_bam_stream_header.restype = C.c_int32
-    lib.bsdc_bam_writer_open.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_int32, _P, _P, _P, C.c_int32,
-                                         C.POINTER(_P)]
-    lib.bsdc_bam_writer_open.restype = C.c_int32
-    lib.bsdc_bam_writer_add.argtypes = [_P, C.POINTER(_Records), C.c_int32]
-    lib.bsdc_bam_writer_add.restype = C.c_int32
-    lib.bsdc_bam_writer_encode.argtypes = [_P, C.POINTER(_Records), C.c_int32, C.POINTER(C.c_void_p)]
-    lib.bsdc_bam_writer_encode.restype = C.c_int64
-    lib.bsdc_bam_writer_take.argtypes = [_P, C.c_int64, _P, _P, C.c_int32]
-    lib.bsdc_bam_writer_take.restype = C.c_int32
-    lib.bsdc_bam_writer_put.argtypes = [_P, C.c_int64, _P, _P, _P, _P, C.c_int32]
-    lib.bsdc_bam_writer_put.restype = C.c_int32
-    lib.bsdc_fastq_writer_encode.argtypes = [_P, C.POINTER(_Records), C.c_int32, _P]
-    lib.bsdc_fastq_writer_encode.restype = C.c_int32
-    lib.bsdc_fastq_writer_take.argtypes = [_P, C.c_int32, C.c_int64, _P, _P, C.c_int32]
-    lib.bsdc_fastq_writer_take.restype = C.c_int32
-    lib.bsdc_fastq_writer_put.argtypes = [_P, C.c_int32, C.c_int64, _P, _P, _P, _P, C.c_int32]
-    lib.bsdc_fastq_writer_put.restype = C.c_int32
-    lib.bsdc_bam_writer_close.argtypes = [_P, C.c_int32]
-    lib.bsdc_bam_writer_close.restype = C.c_int32
-    lib.bsdc_fastq_writer_open.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(_P)]
-    lib.bsdc_fastq_writer_open.restype = C.c_int32
-    lib.bsdc_fastq_writer_add.argtypes = [_P, C.POINTER(_Records), C.c_int32]
-    lib.bsdc_fastq_writer_add.restype = C.c_int32
-    lib.bsdc_fastq_writer_close.argtypes = [_P, C.c_int32]
-    lib.bsdc_fastq_writer_close.restype = C.c_int32
+    # the streaming writers (what both have, then what one has) and their BGZF sinks
+    rec = C.POINTER(_Records)
+    decl = {"bam_writer_open": [C.c_char_p, C.c_char_p, C.c_int64, C.c_int32, _P, _P, _P, C.c_int32, C.POINTER(_P)],
+            "fastq_writer_open": [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(_P)],
+            "bam_writer_fragment": [_P, C.c_int32], "fastq_writer_fragment": [_P],
+            "bam_writer_raw": [_P, _P, C.c_int64, C.c_int32],
+            "bgzf_sink_take": [_P, C.c_int64, _P, _P, C.c_int32],
+            "bgzf_sink_put": [_P, C.c_int64, _P, _P, _P, _P, C.c_int32]}
+    for kind in ("bam", "fastq"):
+        decl.update({kind + "_writer_add": [_P, rec, C.c_int32], kind + "_writer_encode": [_P, rec, C.c_int32],
+                     kind + "_writer_flush": [_P, C.c_int32], kind + "_writer_close": [_P, C.c_int32]})
+    for name, args in decl.items():
+        fn = getattr(lib, "bsdc_" + name)
+        fn.argtypes, fn.restype = args, C.c_int32
+    lib.bsdc_bam_writer_sink.argtypes, lib.bsdc_bam_writer_sink.restype = [_P], _P
+    lib.bsdc_fastq_writer_sink.argtypes, lib.bsdc_fastq_writer_sink.restype = [_P, C.c_int32], _P
+    lib.bsdc_bgzf_sink_whole.argtypes, lib.bsdc_bgzf_sink_whole.restype = [_P], C.c_int64
+    lib.bsdc_bgzf_sink_tell.argtypes, lib.bsdc_bgzf_sink_tell.restype = [_P], C.c_int64
     lib.bsdc_bam_write.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_int32, _P, _P, _P, C.POINTER(_Records),
                                    C.c_int32, C.c_int32]
     lib.bsdc_bam_write.restype = C.c_int32
@@ -157,22 +150,8 @@ def _load():
     lib.bsdc_bam_rec_keys.restype = C.c_int32
     lib.bsdc_spill_sort.argtypes = [_P, C.c_int64, _P, _P]
     lib.bsdc_spill_sort.restype = C.c_int64
-    lib.bsdc_bam_writer_flush.argtypes = [_P, C.c_int32]
-    lib.bsdc_bam_writer_flush.restype = C.c_int32
-    lib.bsdc_bam_writer_tell.argtypes = [_P]
-    lib.bsdc_bam_writer_tell.restype = C.c_int64
-    lib.bsdc_bam_writer_raw.argtypes = [_P, _P, C.c_int64, C.c_int32]
-    lib.bsdc_bam_writer_raw.restype = C.c_int32
-    lib.bsdc_fastq_writer_flush.argtypes = [_P, C.c_int32]
-    lib.bsdc_fastq_writer_flush.restype = C.c_int32
-    lib.bsdc_fastq_writer_tell.argtypes = [_P, _P]
-    lib.bsdc_fastq_writer_tell.restype = None
     lib.bsdc_bam_stream_range_stats.argtypes = [_P, _P]
     lib.bsdc_bam_stream_range_stats.restype = None
-    lib.bsdc_bam_writer_fragment.argtypes = [_P, C.c_int32]
-    lib.bsdc_bam_writer_fragment.restype = C.c_int32
-    lib.bsdc_fastq_writer_fragment.argtypes = [_P]
-    lib.bsdc_fastq_writer_fragment.restype = C.c_int32
     if lib.bsdc_io_abi_version() != BSDC_IO_ABI_VERSION:
         raise RuntimeError("libbsdc_io ABI %d != %d" % (lib.bsdc_io_abi_version(), BSDC_IO_ABI_VERSION))
     _lib = lib
@@ -726,13 +705,27 @@ def records_to_bam(raw: R.RawRecords) -> OutRecordsBam:
                          raw.cigar, seq_off, raw.seq, raw.qual, aux)
 
 
+def _c_array(keep: list, x, dt):
+    """x as a contiguous dt array (kept alive in `keep`; one element if empty) -> its pointer."""
+    a = np.ascontiguousarray(x, dtype=dt)
+    if a.size == 0:
+        a = np.zeros(1, dt)
+    keep.append(a)
+    return _ptr(a)
+
+
+def _header_args(header: BamHeader, keep: list) -> tuple:
+    """bsdc_bam_write's / bsdc_bam_writer_open's header arguments: text, its length, n_ref, the
+    reference names' offsets and bytes, the reference lengths."""
+    rn = StringTable.from_list([x.encode() for x in header.ref_names])
+    text = header.text.encode()
+    return (text, len(text), len(header.ref_names), _c_array(keep, rn.off, np.int64), _c_array(keep, rn.buf, np.uint8),
+            _c_array(keep, np.asarray(header.ref_lens, np.int64), np.int64))
+
+
 def _records_struct(recs: OutRecordsBam, keep: list) -> _Records:
     def c(x, dt):
-        a = np.ascontiguousarray(x, dtype=dt)
-        if a.size == 0:
-            a = np.zeros(1, dt)
-        keep.append(a)
-        return _ptr(a)
+        return _c_array(keep, x, dt)
     return _Records(recs.n, c(recs.flag, np.uint16), c(recs.tid, np.int32), c(recs.pos, np.int32),
                     c(recs.mapq, np.uint8), c(recs.next_tid, np.int32), c(recs.next_pos, np.int32),
                     c(recs.tlen, np.int32), c(recs.names.off, np.int64), c(recs.names.buf, np.uint8),
@@ -777,20 +770,9 @@ def write_fastq(path1: str, path2: str, recs: OutRecordsBam, level: int = 6, thr
 
 def write_bam(path: str, header: BamHeader, recs: OutRecordsBam, level: int = 6, threads: int = 0):
     lib = _load()
-    rn = StringTable.from_list([x.encode() for x in header.ref_names])
     keep = []
-
-    def c(x, dt):
-        a = np.ascontiguousarray(x, dtype=dt)
-        if a.size == 0:
-            a = np.zeros(1, dt)
-        keep.append(a)
-        return _ptr(a)
     r = _records_struct(recs, keep)
-    text = header.text.encode()
-    rc = lib.bsdc_bam_write(path.encode(), text, len(text), len(header.ref_names), c(rn.off, np.int64),
-                            c(rn.buf, np.uint8), c(np.asarray(header.ref_lens, np.int64), np.int64), C.byref(r),
-                            int(level), int(threads))
+    rc = lib.bsdc_bam_write(path.encode(), *_header_args(header, keep), C.byref(r), int(level), int(threads))
     if rc != 0:
         raise OSError("%s: %s" % (path, lib.bsdc_io_last_error().decode()))
 
@@ -966,38 +948,27 @@ class GpuInflate:
                 "seconds": round(self.seconds, 4)}
 
 
-class BamWriter:
-    """Streaming BAM writer (bsdc_bam_writer): header at open, records added in order, the same
-    bytes as write_bam of all the records at once -- or, with `gpu` (a GpuBgzf), every whole block
-    deflated on the GPU (valid BGZF, other compressed bytes), one add's blocks compressing while
-    the next add encodes."""
+class _BgzfWriter:
+    """What the streaming writers share: a C writer (bsdc_<kind>_writer) over one BGZF sink per
+    file (bsdc_bgzf_sink).  On the host path an add deflates the whole blocks it fills.  With `gpu`
+    (a GpuBgzf) an add only encodes; the whole blocks of every sink are taken back to back into one
+    pinned staging slot and deflated on the GPU in one job (valid BGZF, other compressed bytes),
+    which is written when the next add, a flush or the close drains it: one add's blocks compress
+    while the next add encodes."""
 
-    def __init__(self, path: str, header: BamHeader, level: int = 6, gpu: Optional["GpuBgzf"] = None,
-                 fragment: Optional[str] = None):
-        """fragment: "first" (header, no EOF block) or "next" (neither) -- one rank's piece of a
-        BAM that ranks.assemble concatenates."""
+    def __init__(self, kind: str, path: str, gpu: Optional["GpuBgzf"], *open_args):
         self.lib = _load()
+        self.kind = kind
         self.path = path
         self.gpu = gpu
-        self.pending = None  # (nblk, crc, raw) submitted to the GPU, not yet written
-        rn = StringTable.from_list([x.encode() for x in header.ref_names])
-        keep = []
-
-        def c(x, dt):
-            a = np.ascontiguousarray(x, dtype=dt)
-            if a.size == 0:
-                a = np.zeros(1, dt)
-            keep.append(a)
-            return _ptr(a)
-        text = header.text.encode()
+        self.pending = None  # (blocks per sink, crc, raw) submitted to the GPU, not yet written
+        self.sinks = []
         self.h = _P()
-        rc = self.lib.bsdc_bam_writer_open(path.encode(), text, len(text), len(header.ref_names), c(rn.off, np.int64),
-                                           c(rn.buf, np.uint8), c(np.asarray(header.ref_lens, np.int64), np.int64),
-                                           int(level), C.byref(self.h))
-        if rc != 0:
-            raise OSError("%s: %s" % (path, self.lib.bsdc_io_last_error().decode()))
-        if fragment is not None and self.lib.bsdc_bam_writer_fragment(self.h, int(fragment == "first")) != 0:
+        if self._call("open", *open_args, C.byref(self.h)) != 0:
             raise self._err()
+
+    def _call(self, what: str, *args):
+        return getattr(self.lib, "bsdc_%s_writer_%s" % (self.kind, what))(*args)
 
     def _err(self):
         return OSError("%s: %s" % (self.path, self.lib.bsdc_io_last_error().decode()))
@@ -1005,51 +976,49 @@ class BamWriter:
     def _drain(self, threads: int):
         if self.pending is None:
             return
-        nblk, crc, raw = self.pending
+        nb, crc, raw = self.pending
         self.pending = None
         packed, sizes = self.gpu.finish()
-        if self.lib.bsdc_bam_writer_put(self.h, nblk, _ptr(packed), _ptr(sizes), _ptr(crc), raw.data_ptr(),
-                                        int(threads)) != 0:
-            raise self._err()
+        b = off = 0  # the blocks / packed bytes of the sinks before this one
+        for sink, n in zip(self.sinks, nb):
+            if n == 0:
+                continue
+            sz = np.ascontiguousarray(sizes[b:b + n])
+            if self.lib.bsdc_bgzf_sink_put(sink, n, packed.ctypes.data + off, _ptr(sz), crc.ctypes.data + 4 * b,
+                                           raw.data_ptr() + b * 65280, int(threads)) != 0:
+                raise self._err()
+            off += int(np.maximum(sz, 0).sum(dtype=np.int64))
+            b += n
 
     def add(self, recs: OutRecordsBam, threads: int = 0):
         keep = []
         r = _records_struct(recs, keep)
-        if self.gpu is None:
-            if self.lib.bsdc_bam_writer_add(self.h, C.byref(r), int(threads)) != 0:
-                raise self._err()
-            return
-        data = C.c_void_p()
-        nbytes = self.lib.bsdc_bam_writer_encode(self.h, C.byref(r), int(threads), C.byref(data))
-        if nbytes < 0:
+        if self._call("add" if self.gpu is None else "encode", self.h, C.byref(r), int(threads)) != 0:
             raise self._err()
-        nblk = int(nbytes) // 65280
+        if self.gpu is None:
+            return
+        nb = [int(self.lib.bsdc_bgzf_sink_whole(sink)) // 65280 for sink in self.sinks]
         job = None
-        if nblk:
-            raw = self.gpu.staging(int(nbytes))
-            crc = np.empty(nblk, np.uint32)
-            if self.lib.bsdc_bam_writer_take(self.h, nblk, raw.data_ptr(), _ptr(crc), int(threads)) != 0:
-                raise self._err()
-            job = (nblk, crc, raw)
+        if sum(nb):
+            raw = self.gpu.staging(sum(nb) * 65280)
+            crc = np.empty(sum(nb), np.uint32)
+            b = 0
+            for sink, n in zip(self.sinks, nb):  # (file 2's blocks follow file 1's)
+                if n and self.lib.bsdc_bgzf_sink_take(sink, n, raw.data_ptr() + b * 65280, crc.ctypes.data + 4 * b,
+                                                      int(threads)) != 0:
+                    raise self._err()
+                b += n
+            job = (nb, crc, raw)
         self._drain(threads)
         if job is not None:
-            self.gpu.submit(job[2], nblk)
+            self.gpu.submit(job[2], sum(nb))
             self.pending = job
 
-    def flush(self, threads: int = 0) -> int:
-        """Everything added so far written as whole BGZF blocks; -> the file's length, a point
-        where it may be cut (ranks.py splices other pieces in there)."""
+    def _flush(self, threads: int) -> tuple:
         self._drain(threads)
-        if self.lib.bsdc_bam_writer_flush(self.h, int(threads)) != 0:
+        if self._call("flush", self.h, int(threads)) != 0:
             raise self._err()
-        return int(self.lib.bsdc_bam_writer_tell(self.h))
-
-    def add_raw(self, data: bytes, threads: int = 0):
-        """Raw BAM records (block_size-prefixed), as a stream chunk holds them (host deflate)."""
-        if data:
-            buf = np.frombuffer(data, np.uint8)
-            if self.lib.bsdc_bam_writer_raw(self.h, _ptr(buf), buf.shape[0], int(threads)) != 0:
-                raise self._err()
+        return tuple(int(self.lib.bsdc_bgzf_sink_tell(sink)) for sink in self.sinks)
 
     def close(self, threads: int = 0):
         if self.h:
@@ -1057,8 +1026,37 @@ class BamWriter:
                 self._drain(threads)
             finally:
                 h, self.h = self.h, _P()
-                if self.lib.bsdc_bam_writer_close(h, int(threads)) != 0:
+                self.sinks = []
+                if self._call("close", h, int(threads)) != 0:
                     raise self._err()
+
+
+class BamWriter(_BgzfWriter):
+    """Streaming BAM writer (bsdc_bam_writer): header at open, records added in order, the same
+    bytes as write_bam of all the records at once -- or, with `gpu`, every whole block deflated on
+    the GPU."""
+
+    def __init__(self, path: str, header: BamHeader, level: int = 6, gpu: Optional["GpuBgzf"] = None,
+                 fragment: Optional[str] = None):
+        """fragment: "first" (header, no EOF block) or "next" (neither) -- one rank's piece of a
+        BAM that ranks.assemble concatenates."""
+        keep = []
+        super().__init__("bam", path, gpu, path.encode(), *_header_args(header, keep), int(level))
+        self.sinks = [self.lib.bsdc_bam_writer_sink(self.h)]
+        if fragment is not None and self.lib.bsdc_bam_writer_fragment(self.h, int(fragment == "first")) != 0:
+            raise self._err()
+
+    def flush(self, threads: int = 0) -> int:
+        """Everything added so far written as whole BGZF blocks; -> the file's length, a point
+        where it may be cut (ranks.py splices other pieces in there)."""
+        return self._flush(threads)[0]
+
+    def add_raw(self, data: bytes, threads: int = 0):
+        """Raw BAM records (block_size-prefixed), as a stream chunk holds them (host deflate)."""
+        if data:
+            buf = np.frombuffer(data, np.uint8)
+            if self.lib.bsdc_bam_writer_raw(self.h, _ptr(buf), buf.shape[0], int(threads)) != 0:
+                raise self._err()
 
 
 def close_quietly(*writers):
@@ -1074,85 +1072,21 @@ def close_quietly(*writers):
             pass
 
 
-class FastqWriter:
+class FastqWriter(_BgzfWriter):
     """Streaming paired-FASTQ writer (bsdc_fastq_writer): the bytes write_fastq writes for all the
-    records at once; every add holds whole pairs.  With `gpu` (a GpuBgzf), the whole blocks of
-    both files are deflated on the GPU in one job (valid BGZF-framed gzip, other compressed
-    bytes), one add's blocks compressing while the next add encodes."""
+    records at once; every add holds whole pairs.  With `gpu`, the whole blocks of both files are
+    deflated on the GPU in one job (BGZF-framed gzip)."""
 
     def __init__(self, path1: str, path2: str, level: int = 6, gpu: Optional["GpuBgzf"] = None,
                  fragment: bool = False):
-        self.lib = _load()
-        self.path = path1
-        self.gpu = gpu
-        self.pending = None  # (nblk per file, crc per file, raw) submitted to the GPU, not yet written
-        self.h = _P()
-        if self.lib.bsdc_fastq_writer_open(path1.encode(), path2.encode(), int(level), C.byref(self.h)) != 0:
-            raise OSError("%s: %s" % (path1, self.lib.bsdc_io_last_error().decode()))
+        super().__init__("fastq", path1, gpu, path1.encode(), path2.encode(), int(level))
+        self.sinks = [self.lib.bsdc_fastq_writer_sink(self.h, d) for d in range(2)]
         if fragment and self.lib.bsdc_fastq_writer_fragment(self.h) != 0:  # (no EOF blocks: ranks.assemble)
             raise self._err()
 
-    def _err(self):
-        return OSError("%s: %s" % (self.path, self.lib.bsdc_io_last_error().decode()))
-
-    def _drain(self, threads: int):
-        if self.pending is None:
-            return
-        nb, crcs, raw = self.pending
-        self.pending = None
-        packed, sizes = self.gpu.finish()
-        n0 = nb[0]
-        o1 = int(np.maximum(sizes[:n0], 0).sum(dtype=np.int64))  # file 2's blocks follow file 1's
-        for d, (lo, po, ro) in enumerate(((0, 0, 0), (n0, o1, n0 * 65280))):
-            if nb[d] == 0:
-                continue
-            sz = np.ascontiguousarray(sizes[lo:lo + nb[d]])
-            if self.lib.bsdc_fastq_writer_put(self.h, d, nb[d], packed.ctypes.data + po, _ptr(sz), _ptr(crcs[d]),
-                                              raw.data_ptr() + ro, int(threads)) != 0:
-                raise self._err()
-
-    def add(self, recs: OutRecordsBam, threads: int = 0):
-        keep = []
-        r = _records_struct(recs, keep)
-        if self.gpu is None:
-            if self.lib.bsdc_fastq_writer_add(self.h, C.byref(r), int(threads)) != 0:
-                raise self._err()
-            return
-        whole = np.zeros(2, np.int64)
-        if self.lib.bsdc_fastq_writer_encode(self.h, C.byref(r), int(threads), _ptr(whole)) != 0:
-            raise self._err()
-        nb = [int(whole[0]) // 65280, int(whole[1]) // 65280]
-        job = None
-        if nb[0] + nb[1]:
-            raw = self.gpu.staging((nb[0] + nb[1]) * 65280)
-            crcs = [np.empty(max(k, 1), np.uint32) for k in nb]
-            for d in range(2):
-                if nb[d] and self.lib.bsdc_fastq_writer_take(self.h, d, nb[d], raw.data_ptr() + (nb[0] * 65280 if d else 0),
-                                                             _ptr(crcs[d]), int(threads)) != 0:
-                    raise self._err()
-            job = (nb, crcs, raw)
-        self._drain(threads)
-        if job is not None:
-            self.gpu.submit(job[2], nb[0] + nb[1])
-            self.pending = job
-
-    def flush(self, threads: int = 0):
+    def flush(self, threads: int = 0) -> Tuple[int, int]:
         """Everything added so far written as whole BGZF blocks; -> (length of file 1, of file 2)."""
-        self._drain(threads)
-        if self.lib.bsdc_fastq_writer_flush(self.h, int(threads)) != 0:
-            raise self._err()
-        out = np.zeros(2, np.int64)
-        self.lib.bsdc_fastq_writer_tell(self.h, _ptr(out))
-        return int(out[0]), int(out[1])
-
-    def close(self, threads: int = 0):
-        if self.h:
-            try:
-                self._drain(threads)
-            finally:
-                h, self.h = self.h, _P()
-                if self.lib.bsdc_fastq_writer_close(h, int(threads)) != 0:
-                    raise self._err()
+        return self._flush(threads)
 
 
 def read_fasta(path: str, header: BamHeader) -> R.Reference:

@@ -2245,14 +2245,110 @@ int32_t deflate_write(FILE *f, const uint8_t *src0, int64_t total, int32_t level
 }
 
 const uint8_t kBgzfEof[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+}  // namespace
 
-int32_t write_bgzf(const char *path, const Bytes &buf, int32_t level) {
-    FILE *f = fopen(path, "wb");
-    if (!f) return fail(BSDC_IO_EIO, std::string("cannot create ") + path);
-    int32_t rc = deflate_write(f, buf.data(), (int64_t)buf.size(), level);
-    if (rc == 0 && fwrite(kBgzfEof, 1, 28, f) != 28) rc = fail(BSDC_IO_EIO, std::string("write failed on ") + path);
-    if (fclose(f) != 0 && rc == 0) rc = fail(BSDC_IO_EIO, std::string("write failed on ") + path);
-    return rc;
+// One BGZF output file, under the BAM writer (one) and the FASTQ writer (two): encoded bytes
+// collect in `tail`; whole kBlock blocks leave it from the front, deflated here (drain_whole) or by
+// the caller (take / put); flush cuts the file at a block boundary; close deflates the rest.
+struct bsdc_bgzf_sink {
+    FILE *f = nullptr;
+    int32_t level = 6;
+    Bytes tail;
+    bool no_eof = false;  // a fragment: no EOF block at the close
+
+    ~bsdc_bgzf_sink() {  // (a sink dropped without close(): a failed open of its writer)
+        if (f) fclose(f);
+    }
+    int32_t open(const char *path, int32_t lvl) {
+        level = lvl;
+        f = fopen(path, "wb");
+        return f ? 0 : fail(BSDC_IO_EIO, std::string("cannot create ") + path);
+    }
+    int64_t whole_bytes() const { return ((int64_t)tail.size() / kBlock) * kBlock; }
+    // the first n bytes of the tail deflated (in parallel) and written, then erased
+    int32_t drain(int64_t n) {
+        if (n <= 0) return 0;
+        const int32_t rc = deflate_write(f, tail.data(), n, level);
+        if (rc == 0) tail.erase(tail.begin(), tail.begin() + n);
+        return rc;
+    }
+    int32_t drain_whole() { return drain(whole_bytes()); }
+    // Everything appended so far leaves as BGZF blocks (the last one short) and reaches the file,
+    // so it can be cut at tell().
+    int32_t flush() {
+        const int32_t rc = drain((int64_t)tail.size());
+        return rc == 0 && fflush(f) != 0 ? fail(BSDC_IO_EIO, "BGZF write failed") : rc;
+    }
+    int64_t tell() const { return (int64_t)ftello(f); }
+    int32_t close() {
+        int32_t rc = flush();
+        if (rc == 0 && !no_eof && fwrite(kBgzfEof, 1, 28, f) != 28) rc = fail(BSDC_IO_EIO, "BGZF write failed");
+        if (fclose(f) != 0 && rc == 0) rc = fail(BSDC_IO_EIO, "BGZF close failed");
+        f = nullptr;
+        return rc;
+    }
+
+    // The first nblk whole blocks leave the tail: copied to dst (nblk * 65280 bytes) with each
+    // block's CRC32 in crc[b] (one pass over the bytes, the blocks in parallel).
+    int32_t take(int64_t nblk, uint8_t *dst, uint32_t *crc) {
+        if (nblk < 0 || nblk * kBlock > (int64_t)tail.size()) return fail(BSDC_IO_EFORMAT, "more blocks than encoded bytes");
+        const uint8_t *src0 = tail.data();
+#pragma omp parallel for schedule(static)
+        for (int64_t b = 0; b < nblk; b++) {
+            memcpy(dst + b * kBlock, src0 + b * kBlock, (size_t)kBlock);
+            crc[b] = crc32_of(dst + b * kBlock, kBlock);
+        }
+        tail.erase(tail.begin(), tail.begin() + nblk * kBlock);
+        return 0;
+    }
+
+    // nblk taken blocks back compressed: block b's BGZF bytes are packed[off_b .. off_b + sizes[b])
+    // (off = running sum of sizes), complete but for CRC32 and ISIZE, which are filled in here from
+    // crc[b]; a block of size 0 did not fit and is deflated here from raw (the taken bytes; stored
+    // when incompressible).  Then the blocks are written in order.
+    int32_t put(int64_t nblk, uint8_t *packed, const int32_t *sizes, const uint32_t *crc, const uint8_t *raw) {
+        int64_t off = 0;
+        for (int64_t b = 0; b < nblk; b++) {
+            const int32_t bs = sizes[b];
+            int32_t rc = 0;
+            if (bs > 0) {
+                if (bs < 26 || bs > 65536) return fail(BSDC_IO_EFORMAT, "bad compressed block size");
+                uint8_t *h = packed + off;
+                wr32(h + bs - 8, crc[b]);
+                wr32(h + bs - 4, (uint32_t)kBlock);
+                if (fwrite(h, 1, (size_t)bs, f) != (size_t)bs) rc = fail(BSDC_IO_EIO, "BGZF write failed");
+                off += bs;
+            } else {
+                rc = deflate_write(f, raw + b * kBlock, kBlock, level);
+            }
+            if (rc != 0) return rc;
+        }
+        return 0;
+    }
+};
+
+extern "C" {
+int64_t bsdc_bgzf_sink_whole(bsdc_bgzf_sink *s) { return s->whole_bytes(); }
+int32_t bsdc_bgzf_sink_take(bsdc_bgzf_sink *s, int64_t nblk, uint8_t *dst, uint32_t *crc, int32_t n_threads) {
+    set_threads(n_threads);
+    return s->take(nblk, dst, crc);
+}
+int32_t bsdc_bgzf_sink_put(bsdc_bgzf_sink *s, int64_t nblk, uint8_t *packed, const int32_t *sizes, const uint32_t *crc,
+                           const uint8_t *raw, int32_t n_threads) {
+    set_threads(n_threads);
+    return s->put(nblk, packed, sizes, crc, raw);
+}
+int64_t bsdc_bgzf_sink_tell(bsdc_bgzf_sink *s) { return s->tell(); }
+}  // extern "C"
+
+namespace {
+// buf (emptied) as one whole BGZF file with its EOF block
+int32_t write_bgzf(const char *path, Bytes &buf, int32_t level) {
+    bsdc_bgzf_sink s;
+    const int32_t rc = s.open(path, level);
+    if (rc != 0) return rc;
+    s.tail.swap(buf);
+    return s.close();
 }
 
 // BAM header bytes (magic, text, references)
@@ -2353,144 +2449,67 @@ extern "C" int32_t bsdc_bam_write(const char *path, const char *header_text, int
 // blocks are deflated as they fill; the rest waits for the next records or the close)
 // ------------------------------------------------------------------------------------------
 struct bsdc_bam_writer {
-    FILE *f = nullptr;
-    int32_t level = 6;
-    Bytes tail;
-    bool no_eof = false;  // a fragment (bsdc_bam_writer_fragment): no EOF block at the close
+    bsdc_bgzf_sink s;
 };
 
 extern "C" int32_t bsdc_bam_writer_open(const char *path, const char *header_text, int64_t header_len, int32_t n_ref,
                                         const int64_t *ref_name_off, const char *ref_name_buf, const int64_t *ref_len,
                                         int32_t level, bsdc_bam_writer **out) {
     *out = nullptr;
-    FILE *f = fopen(path, "wb");
-    if (!f) return fail(BSDC_IO_EIO, std::string("cannot create ") + path);
     auto *w = new bsdc_bam_writer();
-    w->f = f;
-    w->level = level;
-    encode_header(w->tail, header_text, header_len, n_ref, ref_name_off, ref_name_buf, ref_len);
+    const int32_t rc = w->s.open(path, level);
+    if (rc != 0) {
+        delete w;
+        return rc;
+    }
+    encode_header(w->s.tail, header_text, header_len, n_ref, ref_name_off, ref_name_buf, ref_len);
     *out = w;
     return 0;
 }
 
-extern "C" int32_t bsdc_bam_writer_add(bsdc_bam_writer *w, const bsdc_bam_records *r, int32_t n_threads) {
-    set_threads(n_threads);
-    int32_t rc = encode_records(r, w->tail);
-    if (rc != 0) return rc;
-    const int64_t whole = ((int64_t)w->tail.size() / kBlock) * kBlock;
-    if (whole > 0) {
-        rc = deflate_write(w->f, w->tail.data(), whole, w->level);
-        if (rc != 0) return rc;
-        w->tail.erase(w->tail.begin(), w->tail.begin() + whole);
-    }
-    return 0;
-}
+extern "C" bsdc_bgzf_sink *bsdc_bam_writer_sink(bsdc_bam_writer *w) { return &w->s; }
 
 // The GPU-compressed write path (bsdc_bgzf_deflate in libbsdc): encode, move the whole blocks out
-// to the caller's (pinned) buffer with their CRC32s, let the caller compress them on the GPU while
-// the next records encode, then hand the compressed blocks back to be finished and written.
-extern "C" int64_t bsdc_bam_writer_encode(bsdc_bam_writer *w, const bsdc_bam_records *r, int32_t n_threads,
-                                          const uint8_t **data) {
+// to the caller's (pinned) buffer with their CRC32s (bsdc_bgzf_sink_take), let the caller compress
+// them on the GPU while the next records encode, then hand the compressed blocks back to be
+// finished and written (bsdc_bgzf_sink_put).
+extern "C" int32_t bsdc_bam_writer_encode(bsdc_bam_writer *w, const bsdc_bam_records *r, int32_t n_threads) {
     set_threads(n_threads);
-    const int32_t rc = encode_records(r, w->tail);
-    if (rc != 0) return rc;
-    *data = w->tail.data();
-    return ((int64_t)w->tail.size() / kBlock) * kBlock;
+    return encode_records(r, w->s.tail);
 }
 
-namespace {
-// The first nblk whole blocks of an encoded tail leave it: copied to dst (nblk * 65280 bytes) with
-// each block's CRC32 in crc[b] (one pass over the bytes, the blocks in parallel).
-int32_t take_blocks(Bytes &tail, int64_t nblk, uint8_t *dst, uint32_t *crc) {
-    if (nblk < 0 || nblk * kBlock > (int64_t)tail.size()) return fail(BSDC_IO_EFORMAT, "more blocks than encoded bytes");
-    const uint8_t *src0 = tail.data();
-#pragma omp parallel for schedule(static)
-    for (int64_t b = 0; b < nblk; b++) {
-        memcpy(dst + b * kBlock, src0 + b * kBlock, (size_t)kBlock);
-        crc[b] = crc32_of(dst + b * kBlock, kBlock);
-    }
-    tail.erase(tail.begin(), tail.begin() + nblk * kBlock);
-    return 0;
+extern "C" int32_t bsdc_bam_writer_add(bsdc_bam_writer *w, const bsdc_bam_records *r, int32_t n_threads) {
+    const int32_t rc = bsdc_bam_writer_encode(w, r, n_threads);
+    return rc != 0 ? rc : w->s.drain_whole();
 }
-
-// nblk taken blocks back compressed: block b's BGZF bytes are packed[off_b .. off_b + sizes[b])
-// (off = running sum of sizes), complete but for CRC32 and ISIZE, which are filled in here from
-// crc[b]; a block of size 0 did not fit and is deflated here from raw (the taken bytes; stored when
-// incompressible).  Then the blocks are written in order.
-int32_t put_blocks(FILE *f, int32_t level, int64_t nblk, uint8_t *packed, const int32_t *sizes, const uint32_t *crc,
-                   const uint8_t *raw) {
-    int64_t off = 0;
-    for (int64_t b = 0; b < nblk; b++) {
-        const int32_t bs = sizes[b];
-        int32_t rc = 0;
-        if (bs > 0) {
-            if (bs < 26 || bs > 65536) return fail(BSDC_IO_EFORMAT, "bad compressed block size");
-            uint8_t *h = packed + off;
-            wr32(h + bs - 8, crc[b]);
-            wr32(h + bs - 4, (uint32_t)kBlock);
-            if (fwrite(h, 1, (size_t)bs, f) != (size_t)bs) rc = fail(BSDC_IO_EIO, "BGZF write failed");
-            off += bs;
-        } else {
-            rc = deflate_write(f, raw + b * kBlock, kBlock, level);
-        }
-        if (rc != 0) return rc;
-    }
-    return 0;
-}
-}  // namespace
-
-extern "C" int32_t bsdc_bam_writer_take(bsdc_bam_writer *w, int64_t nblk, uint8_t *dst, uint32_t *crc,
-                                        int32_t n_threads) {
-    set_threads(n_threads);
-    return take_blocks(w->tail, nblk, dst, crc);
-}
-
-extern "C" int32_t bsdc_bam_writer_put(bsdc_bam_writer *w, int64_t nblk, uint8_t *packed, const int32_t *sizes,
-                                       const uint32_t *crc, const uint8_t *raw, int32_t n_threads) {
-    set_threads(n_threads);
-    return put_blocks(w->f, w->level, nblk, packed, sizes, crc, raw);
-}
-
-extern "C" int32_t bsdc_bam_writer_close(bsdc_bam_writer *w, int32_t n_threads) {
-    if (!w) return 0;
-    set_threads(n_threads);
-    int32_t rc = deflate_write(w->f, w->tail.data(), (int64_t)w->tail.size(), w->level);
-    if (rc == 0 && !w->no_eof && fwrite(kBgzfEof, 1, 28, w->f) != 28) rc = fail(BSDC_IO_EIO, "BGZF write failed");
-    if (fclose(w->f) != 0 && rc == 0) rc = fail(BSDC_IO_EIO, "BGZF close failed");
-    delete w;
-    return rc;
-}
-
-// Everything added so far leaves as BGZF blocks (the last one short), so the file can be cut here.
-extern "C" int32_t bsdc_bam_writer_flush(bsdc_bam_writer *w, int32_t n_threads) {
-    set_threads(n_threads);
-    const int32_t rc = deflate_write(w->f, w->tail.data(), (int64_t)w->tail.size(), w->level);
-    w->tail.clear();
-    return rc;
-}
-
-extern "C" int64_t bsdc_bam_writer_tell(bsdc_bam_writer *w) { return (int64_t)ftello(w->f); }
 
 // Raw BAM records (block_size-prefixed, as a stream chunk holds them) appended as they are.
 extern "C" int32_t bsdc_bam_writer_raw(bsdc_bam_writer *w, const uint8_t *data, int64_t n, int32_t n_threads) {
     set_threads(n_threads);
-    w->tail.insert(w->tail.end(), data, data + n);
-    const int64_t whole = ((int64_t)w->tail.size() / kBlock) * kBlock;
-    if (whole > 0) {
-        const int32_t rc = deflate_write(w->f, w->tail.data(), whole, w->level);
-        if (rc != 0) return rc;
-        w->tail.erase(w->tail.begin(), w->tail.begin() + whole);
-    }
-    return 0;
+    w->s.tail.insert(w->s.tail.end(), data, data + n);
+    return w->s.drain_whole();
 }
 
 // A writer of one piece of a BAM whose pieces are concatenated later: header or not (keep_header:
 // the first piece), no EOF block at the close (the assembler appends one).
 extern "C" int32_t bsdc_bam_writer_fragment(bsdc_bam_writer *w, int32_t keep_header) {
     if (!w) return fail(BSDC_IO_EFORMAT, "no writer");
-    if (!keep_header) w->tail.clear();  // (nothing but the header is encoded at the open)
-    w->no_eof = true;
+    if (!keep_header) w->s.tail.clear();  // (nothing but the header is encoded at the open)
+    w->s.no_eof = true;
     return 0;
+}
+
+extern "C" int32_t bsdc_bam_writer_flush(bsdc_bam_writer *w, int32_t n_threads) {
+    set_threads(n_threads);
+    return w->s.flush();
+}
+
+extern "C" int32_t bsdc_bam_writer_close(bsdc_bam_writer *w, int32_t n_threads) {
+    if (!w) return 0;
+    set_threads(n_threads);
+    const int32_t rc = w->s.close();
+    delete w;
+    return rc;
 }
 
 namespace {
@@ -2843,100 +2862,62 @@ extern "C" int32_t bsdc_fastq_write(const char *path1, const char *path2, const 
 
 // streaming paired-FASTQ writer: the bytes of bsdc_fastq_write over all the records at once
 struct bsdc_fastq_writer {
-    FILE *f[2] = {nullptr, nullptr};
-    int32_t level = 6;
-    Bytes tail[2];
-    bool no_eof = false;  // a fragment: no EOF block at the close
+    bsdc_bgzf_sink s[2];
 };
 
 extern "C" int32_t bsdc_fastq_writer_open(const char *path1, const char *path2, int32_t level, bsdc_fastq_writer **out) {
     *out = nullptr;
     auto *w = new bsdc_fastq_writer();
-    w->level = level;
     for (int d = 0; d < 2; d++) {
-        w->f[d] = fopen(d == 0 ? path1 : path2, "wb");
-        if (!w->f[d]) {
-            if (d == 1) fclose(w->f[0]);
-            delete w;
-            return fail(BSDC_IO_EIO, std::string("cannot create ") + (d == 0 ? path1 : path2));
+        const int32_t rc = w->s[d].open(d == 0 ? path1 : path2, level);
+        if (rc != 0) {
+            delete w;  // (closes file 1 when file 2 failed)
+            return rc;
         }
     }
     *out = w;
     return 0;
 }
 
+extern "C" bsdc_bgzf_sink *bsdc_fastq_writer_sink(bsdc_fastq_writer *w, int32_t which) {
+    return which == 0 || which == 1 ? &w->s[which] : nullptr;
+}
+
+// The records' FASTQ text appended to the two tails (the GPU-compressed path, as for the BAM writer)
+extern "C" int32_t bsdc_fastq_writer_encode(bsdc_fastq_writer *w, const bsdc_bam_records *r, int32_t n_threads) {
+    set_threads(n_threads);
+    Bytes t[2] = {std::move(w->s[0].tail), std::move(w->s[1].tail)};  // (format_fastq fills a pair of buffers)
+    const int32_t rc = format_fastq(r, t);
+    for (int d = 0; d < 2; d++) w->s[d].tail = std::move(t[d]);
+    return rc;
+}
+
 extern "C" int32_t bsdc_fastq_writer_add(bsdc_fastq_writer *w, const bsdc_bam_records *r, int32_t n_threads) {
-    set_threads(n_threads);
-    int32_t rc = format_fastq(r, w->tail);
-    if (rc != 0) return rc;
-    for (int d = 0; d < 2; d++) {
-        const int64_t whole = ((int64_t)w->tail[d].size() / kBlock) * kBlock;
-        if (whole > 0) {
-            rc = deflate_write(w->f[d], w->tail[d].data(), whole, w->level);
-            if (rc != 0) return rc;
-            w->tail[d].erase(w->tail[d].begin(), w->tail[d].begin() + whole);
-        }
-    }
+    int32_t rc = bsdc_fastq_writer_encode(w, r, n_threads);
+    for (int d = 0; d < 2 && rc == 0; d++) rc = w->s[d].drain_whole();
+    return rc;
+}
+
+extern "C" int32_t bsdc_fastq_writer_fragment(bsdc_fastq_writer *w) {
+    if (!w) return fail(BSDC_IO_EFORMAT, "no writer");
+    w->s[0].no_eof = w->s[1].no_eof = true;
     return 0;
 }
 
-// The same with the whole blocks compressed by the caller (bsdc_bam_writer_encode / take / put for
-// the two files): whole[d] = the bytes of whole blocks now at the front of file d's tail.
-extern "C" int32_t bsdc_fastq_writer_encode(bsdc_fastq_writer *w, const bsdc_bam_records *r, int32_t n_threads,
-                                            int64_t *whole) {
+extern "C" int32_t bsdc_fastq_writer_flush(bsdc_fastq_writer *w, int32_t n_threads) {
     set_threads(n_threads);
-    const int32_t rc = format_fastq(r, w->tail);
-    if (rc != 0) return rc;
-    for (int d = 0; d < 2; d++) whole[d] = ((int64_t)w->tail[d].size() / kBlock) * kBlock;
-    return 0;
-}
-
-extern "C" int32_t bsdc_fastq_writer_take(bsdc_fastq_writer *w, int32_t which, int64_t nblk, uint8_t *dst, uint32_t *crc,
-                                          int32_t n_threads) {
-    set_threads(n_threads);
-    if (which != 0 && which != 1) return fail(BSDC_IO_EFORMAT, "no such FASTQ file");
-    return take_blocks(w->tail[which], nblk, dst, crc);
-}
-
-extern "C" int32_t bsdc_fastq_writer_put(bsdc_fastq_writer *w, int32_t which, int64_t nblk, uint8_t *packed,
-                                         const int32_t *sizes, const uint32_t *crc, const uint8_t *raw,
-                                         int32_t n_threads) {
-    set_threads(n_threads);
-    if (which != 0 && which != 1) return fail(BSDC_IO_EFORMAT, "no such FASTQ file");
-    return put_blocks(w->f[which], w->level, nblk, packed, sizes, crc, raw);
+    int32_t rc = 0;
+    for (int d = 0; d < 2 && rc == 0; d++) rc = w->s[d].flush();
+    return rc;
 }
 
 extern "C" int32_t bsdc_fastq_writer_close(bsdc_fastq_writer *w, int32_t n_threads) {
     if (!w) return 0;
     set_threads(n_threads);
     int32_t rc = 0;
-    for (int d = 0; d < 2; d++) {
-        if (rc == 0) rc = deflate_write(w->f[d], w->tail[d].data(), (int64_t)w->tail[d].size(), w->level);
-        if (rc == 0 && !w->no_eof && fwrite(kBgzfEof, 1, 28, w->f[d]) != 28) rc = fail(BSDC_IO_EIO, "BGZF write failed");
-        if (fclose(w->f[d]) != 0 && rc == 0) rc = fail(BSDC_IO_EIO, "BGZF close failed");
-    }
-    delete w;
+    for (int d = 0; d < 2 && rc == 0; d++) rc = w->s[d].close();
+    delete w;  // (after an error, closes what is still open)
     return rc;
-}
-
-extern "C" int32_t bsdc_fastq_writer_fragment(bsdc_fastq_writer *w) {
-    if (!w) return fail(BSDC_IO_EFORMAT, "no writer");
-    w->no_eof = true;
-    return 0;
-}
-
-extern "C" int32_t bsdc_fastq_writer_flush(bsdc_fastq_writer *w, int32_t n_threads) {
-    set_threads(n_threads);
-    for (int d = 0; d < 2; d++) {
-        const int32_t rc = deflate_write(w->f[d], w->tail[d].data(), (int64_t)w->tail[d].size(), w->level);
-        w->tail[d].clear();
-        if (rc != 0) return rc;
-    }
-    return 0;
-}
-
-extern "C" void bsdc_fastq_writer_tell(bsdc_fastq_writer *w, int64_t *out) {
-    for (int d = 0; d < 2; d++) out[d] = (int64_t)ftello(w->f[d]);
 }
 
 // Packed byte tables (entry r of a table = buf[off[r], off[r + 1])): per entry, the concatenation

@@ -240,7 +240,7 @@ void bsdc_phred_buckets(double error_rate_pre_umi, double error_rate_post_umi, u
    device bytes in[0, n) as blocks of 65280 bytes, one dynamic-Huffman DEFLATE block each.
    bsdc_bgzf_deflate compresses blocks blk0 .. blk0 + nblk - 1 into the scratch
    (bsdc_bgzf_scratch_bytes(nblk) bytes) and writes sizes[blk0 + b]: the BGZF block size, its
-   CRC32 / ISIZE trailer counted but left to the host (libbsdc_io bsdc_bam_writer_put), or
+   CRC32 / ISIZE trailer counted but left to the host (libbsdc_io bsdc_bgzf_sink_put), or
    0 when the block does not fit (the host deflates it).  bsdc_bgzf_pack then copies block b's
    bytes from the scratch to out + (sizes[0] + .. + sizes[blk0 + b - 1]), so successive launches
    over one stream's blocks pack them back to back with no host round trip.  Device pointers;

@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define BSDC_IO_ABI_VERSION 13
+#define BSDC_IO_ABI_VERSION 14
 #define BSDC_IO_EFORMAT (-10) /* not BGZF/BAM, truncated, bad CRC */
 #define BSDC_IO_EIO (-11)     /* open/read/write failed */
 #define BSDC_IO_EINVAL (-22)  /* bad argument */
@@ -221,32 +221,41 @@ int32_t bsdc_bam_write(const char *path, const char *header_text, int64_t header
                        const int64_t *ref_name_off, const char *ref_name_buf, const int64_t *ref_len,
                        const bsdc_bam_records *r, int32_t level, int32_t n_threads);
 
+/* (IO ABI 14) One BGZF output file under a streaming writer (the BAM writer has one, the FASTQ writer two):
+ * what the writer encodes collects in the sink's tail, and whole 65280-byte blocks leave it from
+ * the front -- deflated on the host by the writer's add, or by the caller (on the GPU:
+ * bsdc_bgzf_deflate in libbsdc) between the writer's encode and these: whole = the byte count of
+ * whole blocks now at the front of the tail; take moves the first nblk of them to dst with their
+ * CRC32s; put writes nblk taken blocks back compressed -- block b's BGZF bytes packed back to
+ * back, sizes[b] each with the CRC32 / ISIZE bytes still to fill (from crc[b]), 0 = deflate it
+ * here from raw (what take copied) -- in order.  Takes and puts come in the same order.  tell =
+ * the file's bytes written (after the writer's flush, a point where the file may be cut).  A sink
+ * lives as long as its writer. */
+typedef struct bsdc_bgzf_sink bsdc_bgzf_sink;
+int64_t bsdc_bgzf_sink_whole(bsdc_bgzf_sink *s);
+int32_t bsdc_bgzf_sink_take(bsdc_bgzf_sink *s, int64_t nblk, uint8_t *dst, uint32_t *crc, int32_t n_threads);
+int32_t bsdc_bgzf_sink_put(bsdc_bgzf_sink *s, int64_t nblk, uint8_t *packed, const int32_t *sizes, const uint32_t *crc,
+                           const uint8_t *raw, int32_t n_threads);
+int64_t bsdc_bgzf_sink_tell(bsdc_bgzf_sink *s);
+
 /* Streaming writer: the bytes bsdc_bam_write writes for all the records at once, written as
- * records are added (whole BGZF blocks deflated in parallel as they fill). */
+ * records are added (whole BGZF blocks deflated in parallel as they fill).  encode = add without
+ * the deflate: the records' bytes only join the sink's tail. */
 typedef struct bsdc_bam_writer bsdc_bam_writer;
 int32_t bsdc_bam_writer_open(const char *path, const char *header_text, int64_t header_len, int32_t n_ref,
                              const int64_t *ref_name_off, const char *ref_name_buf, const int64_t *ref_len,
                              int32_t level, bsdc_bam_writer **out);
+bsdc_bgzf_sink *bsdc_bam_writer_sink(bsdc_bam_writer *w);
 int32_t bsdc_bam_writer_add(bsdc_bam_writer *w, const bsdc_bam_records *r, int32_t n_threads);
-/* The same with the whole blocks compressed by the caller (on the GPU: bsdc_bgzf_deflate in
- * libbsdc): encode returns the byte count of whole 65280-byte blocks now at the front of the tail
- * (*data: valid until the next call); take moves the first nblk of them to dst with their CRC32s;
- * put writes nblk taken blocks back compressed -- block b's BGZF bytes packed back to back,
- * sizes[b] each with the CRC32 / ISIZE bytes still to fill (from crc[b]), 0 = deflate it here from
- * raw (what take copied) -- in order.  Takes and puts come in the same order. */
-int64_t bsdc_bam_writer_encode(bsdc_bam_writer *w, const bsdc_bam_records *r, int32_t n_threads, const uint8_t **data);
-int32_t bsdc_bam_writer_take(bsdc_bam_writer *w, int64_t nblk, uint8_t *dst, uint32_t *crc, int32_t n_threads);
-int32_t bsdc_bam_writer_put(bsdc_bam_writer *w, int64_t nblk, uint8_t *packed, const int32_t *sizes,
-                            const uint32_t *crc, const uint8_t *raw, int32_t n_threads);
+int32_t bsdc_bam_writer_encode(bsdc_bam_writer *w, const bsdc_bam_records *r, int32_t n_threads);
 int32_t bsdc_bam_writer_close(bsdc_bam_writer *w, int32_t n_threads);
 /* A writer of one piece of a BAM assembled later (ranks.py): keep_header 0 drops the header
  * encoded at the open; no EOF block at the close.  Call right after the open. */
 int32_t bsdc_bam_writer_fragment(bsdc_bam_writer *w, int32_t keep_header);
-/* (IO ABI 11) flush: everything added so far leaves as BGZF blocks (the last one short), so the
- * file may be cut at tell() (its bytes written); raw: block_size-prefixed BAM records appended as
- * they are (a spill file). */
+/* flush: everything added so far leaves as BGZF blocks (the last one short), so the file may be
+ * cut at its sink's tell; raw: block_size-prefixed BAM records appended as they are (a spill
+ * file). */
 int32_t bsdc_bam_writer_flush(bsdc_bam_writer *w, int32_t n_threads);
-int64_t bsdc_bam_writer_tell(bsdc_bam_writer *w);
 int32_t bsdc_bam_writer_raw(bsdc_bam_writer *w, const uint8_t *data, int64_t n, int32_t n_threads);
 
 /* Paired FASTQ of records, as picard SamToFastq F=path1 F2=path2 writes them (the step after the
@@ -258,22 +267,17 @@ int32_t bsdc_fastq_write(const char *path1, const char *path2, const bsdc_bam_re
                          int32_t n_threads);
 
 /* Streaming paired-FASTQ writer: the bytes bsdc_fastq_write writes for all the records at once
- * (each add must hold whole pairs). */
+ * (each add must hold whole pairs).  Its two sinks: which = 0 (first of pair's file), 1 (second);
+ * NULL for any other.  encode, fragment (no EOF blocks at the close) and flush as for the BAM
+ * writer, on both files. */
 typedef struct bsdc_fastq_writer bsdc_fastq_writer;
 int32_t bsdc_fastq_writer_open(const char *path1, const char *path2, int32_t level, bsdc_fastq_writer **out);
+bsdc_bgzf_sink *bsdc_fastq_writer_sink(bsdc_fastq_writer *w, int32_t which);
 int32_t bsdc_fastq_writer_add(bsdc_fastq_writer *w, const bsdc_bam_records *r, int32_t n_threads);
-/* The FASTQ pair's whole blocks compressed by the caller, as for the BAM writer above: encode
- * reports whole[d], the bytes of whole 65280-byte blocks at the front of file d's tail (d = 0, 1);
- * take / put move and write file `which`'s blocks like bsdc_bam_writer_take / _put. */
-int32_t bsdc_fastq_writer_encode(bsdc_fastq_writer *w, const bsdc_bam_records *r, int32_t n_threads, int64_t *whole);
-int32_t bsdc_fastq_writer_take(bsdc_fastq_writer *w, int32_t which, int64_t nblk, uint8_t *dst, uint32_t *crc,
-                               int32_t n_threads);
-int32_t bsdc_fastq_writer_put(bsdc_fastq_writer *w, int32_t which, int64_t nblk, uint8_t *packed, const int32_t *sizes,
-                              const uint32_t *crc, const uint8_t *raw, int32_t n_threads);
+int32_t bsdc_fastq_writer_encode(bsdc_fastq_writer *w, const bsdc_bam_records *r, int32_t n_threads);
 int32_t bsdc_fastq_writer_close(bsdc_fastq_writer *w, int32_t n_threads);
 int32_t bsdc_fastq_writer_fragment(bsdc_fastq_writer *w);
 int32_t bsdc_fastq_writer_flush(bsdc_fastq_writer *w, int32_t n_threads);
-void bsdc_fastq_writer_tell(bsdc_fastq_writer *w, int64_t *out);  /* out[2]: bytes written per file */ /* no EOF blocks at the close */
 
 /* Packed byte tables (entry r = buf[off[r], off[r + 1])), for the output records: per entry the
  * concatenation of k parts (a table, or a constant when offs[j] is NULL: bufs[j], const_len[j]
