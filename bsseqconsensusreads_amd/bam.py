@@ -32,7 +32,7 @@ from . import records as R
 
 IO_LIB_PATH = os.environ.get("BSDC_IO_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)),
                                                                  "libbsdc_io.so")
-BSDC_IO_ABI_VERSION = 14
+BSDC_IO_ABI_VERSION = 15
 _P = C.c_void_p
 # bsdc_inflate_fn (include/bsdc_io.h): user, comp, n_comp, blk, nblk, out, n_out -> 0 or an error
 INFLATE_FN = C.CFUNCTYPE(C.c_int32, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64)
@@ -97,7 +97,8 @@ def _load():
             "bam_writer_fragment": [_P, C.c_int32], "fastq_writer_fragment": [_P],
             "bam_writer_raw": [_P, _P, C.c_int64, C.c_int32],
             "bgzf_sink_take": [_P, C.c_int64, _P, _P, C.c_int32],
-            "bgzf_sink_put": [_P, C.c_int64, _P, _P, _P, _P, C.c_int32]}
+            "bgzf_sink_put": [_P, C.c_int64, _P, _P, _P, _P, C.c_int32],
+            "bgzf_sink_append": [_P, _P, C.c_int64]}
     for kind in ("bam", "fastq"):
         decl.update({kind + "_writer_add": [_P, rec, C.c_int32], kind + "_writer_encode": [_P, rec, C.c_int32],
                      kind + "_writer_flush": [_P, C.c_int32], kind + "_writer_close": [_P, C.c_int32]})
@@ -108,6 +109,7 @@ def _load():
     lib.bsdc_fastq_writer_sink.argtypes, lib.bsdc_fastq_writer_sink.restype = [_P, C.c_int32], _P
     lib.bsdc_bgzf_sink_whole.argtypes, lib.bsdc_bgzf_sink_whole.restype = [_P], C.c_int64
     lib.bsdc_bgzf_sink_tell.argtypes, lib.bsdc_bgzf_sink_tell.restype = [_P], C.c_int64
+    lib.bsdc_bgzf_sink_take_tail.argtypes, lib.bsdc_bgzf_sink_take_tail.restype = [_P, _P, C.c_int64], C.c_int64
     lib.bsdc_bam_write.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_int32, _P, _P, _P, C.POINTER(_Records),
                                    C.c_int32, C.c_int32]
     lib.bsdc_bam_write.restype = C.c_int32
@@ -757,6 +759,37 @@ def family_image(src_off, length, dst_off, seq, qual, n_slots: int, packed: np.n
         raise ValueError(lib.bsdc_io_last_error().decode())
 
 
+def fastq_offsets(status: np.ndarray, length: np.ndarray, filt: Optional[np.ndarray], name_off: np.ndarray):
+    """-> (off0, off1), int64 [F + 1] each: where family f's bytes start in the FASTQ text of file
+    1 / file 2 that libbsdc's bsdc_fastq_format (or format_fastq here) writes for a batch --
+    8 + name + 2 * length bytes per kept family (filter.kept's rule), none for the others;
+    off[F] = the text's size.  name_off: the families' packed name table offsets [F + 1]."""
+    F = int(status.shape[0])
+    keep = (np.asarray(status) & 1) != 0
+    if filt is not None:
+        keep &= np.asarray(filt) == 0
+    nl = np.diff(np.asarray(name_off, np.int64))
+    out = []
+    for d in range(2):
+        off = np.zeros(F + 1, np.int64)
+        np.cumsum(np.where(keep, 8 + nl + 2 * np.asarray(length, np.int64).reshape(F, 2)[:, d], 0), out=off[1:])
+        out.append(off)
+    return out[0], out[1]
+
+
+def family_names(fam_mi: np.ndarray, mi_names, prefix: str) -> StringTable:
+    """The read name "prefix:MI" of every family (duplex_records' names), a packed table."""
+    ids = np.maximum(np.asarray(fam_mi, np.int64), 0)
+    F = int(ids.shape[0])
+    if isinstance(mi_names, StringTable):
+        mt = _take_table(mi_names, ids)
+    else:
+        uniq, inv = np.unique(ids, return_inverse=True)
+        mt = _take_table(StringTable.from_list([(lambda m: m if isinstance(m, bytes) else m.encode())(
+            mi_names[int(i)]) for i in uniq]), inv) if F else StringTable.from_list([])
+    return _concat_fields([prefix.encode() + b":", (mt.buf, mt.off)], F)
+
+
 def write_fastq(path1: str, path2: str, recs: OutRecordsBam, level: int = 6, threads: int = 0):
     """Paired gzip FASTQ of `recs` as picard SamToFastq F=path1 F2=path2 writes it (the rule after
     step 5, main.snake.py:167-177): '@name/1' / '@name/2', SEQ, '+', QUAL+33 (libbsdc_io)."""
@@ -802,6 +835,12 @@ class GpuBgzf:
         self.blocks = 0
         self.bytes_in = 0
         self.bytes_out = 0
+        self.rem = []  # submit_device: each file's bytes past its last whole block, on the device
+        self.fallback_blocks = 0  # submit_device: blocks the kernel handed back (sizes 0), deflated by the host
+        self.raw_fetched = []  # their ordinals (counted over this object's blocks)
+        # test hook, never set outside the tests: f(first ordinal, nblk) -> the job's blocks whose
+        # size submit_device zeroes after the deflate, so that they take the sink's host deflate
+        self.force_host = None
 
     def _buf(self, name, n, dtype=None, pinned=False):
         torch = self.torch
@@ -861,6 +900,124 @@ class GpuBgzf:
         self.bytes_in += nblk * 65280
         self.bytes_out += total
         return out_h.numpy(), sizes_h
+
+    def submit_device(self, pieces):
+        """launch the compression of text that lies in HBM (bsdc_fastq_format's): pieces[d] = the
+        byte ranges file d gains, in order, each (uint8 device tensor, a, b, event or None: the
+        range is ready once the event is).  Behind each file's remainder the ranges are copied
+        device to device into `din` (file 2's whole blocks after file 1's, as the writers' takes
+        lay them out), bsdc_bgzf_crc32 / bsdc_bgzf_deflate / bsdc_bgzf_pack run over the whole
+        blocks, and each file's new remainder (< 65280 bytes) stays on the device.  -> whole
+        blocks per file; finish_device() collects the job (one in flight)."""
+        torch = self.torch
+        if self.job is not None:
+            raise RuntimeError("GpuBgzf.submit_device with a job in flight")
+        while len(self.rem) < len(pieces):
+            self.rem.append(torch.empty(0, dtype=torch.uint8, device=self.dev))
+        segs = [[self.rem[d]] + [t[a:b] for t, a, b, _ in ps] for d, ps in enumerate(pieces)]
+        nb = [sum(int(x.numel()) for x in sg) // 65280 for sg in segs]
+        nblk = sum(nb)
+        n = nblk * 65280
+        st = self.stream.cuda_stream
+        with torch.cuda.stream(self.stream):
+            for ps in pieces:
+                for t, _, _, ev in ps:
+                    if ev is not None:
+                        self.stream.wait_event(ev)
+                    t.record_stream(self.stream)
+            din = self._buf("din", max(n, 16))
+            pos = 0
+            for d, sg in enumerate(segs):
+                whole = nb[d] * 65280
+                rest = torch.empty(sum(int(x.numel()) for x in sg) - whole, dtype=torch.uint8, device=self.dev)
+                at = 0  # the file's bytes placed so far: the first `whole` into din, the others into rest
+                for x in sg:
+                    k = int(x.numel())
+                    head = min(k, max(whole - at, 0))
+                    if head:
+                        din[pos + at:pos + at + head].copy_(x[:head], non_blocking=True)
+                    if k > head:
+                        r0 = at + head - whole
+                        rest[r0:r0 + k - head].copy_(x[head:], non_blocking=True)
+                    at += k
+                self.rem[d] = rest
+                pos += whole
+            if nblk:
+                out = self._buf("out", nblk * 65536)
+                sizes = self._buf("sizes", nblk, torch.int32)
+                crc = self._buf("crc", nblk, torch.int32)
+                sizes_h = self._buf("sizes_h", nblk, torch.int32, pinned=True)
+                crc_h = self._buf("crc_h", nblk, torch.int32, pinned=True)
+                if self.lib.bsdc_bgzf_crc32(din.data_ptr(), 0, nblk, crc.data_ptr(), st) != 0:
+                    raise RuntimeError("bsdc_bgzf_crc32 failed")
+                back = None if self.force_host is None else np.asarray(self.force_host(self.blocks, nblk), np.int64)
+                for b0 in range(0, nblk, self.MAX_BLOCKS):
+                    k = min(self.MAX_BLOCKS, nblk - b0)
+                    if self.lib.bsdc_bgzf_deflate(din.data_ptr(), n, b0, k, self.scratch.data_ptr(), sizes.data_ptr(),
+                                                  st) != 0:
+                        raise RuntimeError("bsdc_bgzf_deflate failed")
+                    if back is not None and ((back >= b0) & (back < b0 + k)).any():
+                        sizes[torch.from_numpy(back[(back >= b0) & (back < b0 + k)]).to(self.dev)] = 0
+                    if self.lib.bsdc_bgzf_pack(self.scratch.data_ptr(), sizes.data_ptr(), b0, k, out.data_ptr(),
+                                               st) != 0:
+                        raise RuntimeError("bsdc_bgzf_pack failed")
+                sizes_h[:nblk].copy_(sizes[:nblk], non_blocking=True)
+                crc_h[:nblk].copy_(crc[:nblk], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        self.job = (nblk, ev)
+        return nb
+
+    def finish_device(self):
+        """wait for the job of submit_device -> (packed blocks, sizes int32[nblk], crc uint32[nblk],
+        raw: a pinned uint8 array of nblk * 65280 bytes holding the bytes of the blocks whose size
+        is 0 -- for the sink's host deflate -- or None with no such block)."""
+        nblk = self.job[0]
+        first = self.blocks
+        if nblk == 0:
+            self.job[1].synchronize()
+            self.job = None
+            return np.zeros(0, np.uint8), np.zeros(0, np.int32), np.zeros(0, np.uint32), None
+        packed, sizes_h = self.finish()
+        crc = self.buf["crc_h"][:nblk].numpy().view(np.uint32).copy()
+        raw = None
+        zero = np.nonzero(sizes_h == 0)[0]
+        if zero.shape[0]:
+            raw = self._buf("raw_back", nblk * 65280, pinned=True)
+            with self.torch.cuda.stream(self.stream):
+                for b in zero:
+                    raw[int(b) * 65280:(int(b) + 1) * 65280].copy_(self.buf["din"][int(b) * 65280:(int(b) + 1) * 65280],
+                                                                 non_blocking=True)
+            self.stream.synchronize()
+            raw = raw.numpy()
+            self.fallback_blocks += int(zero.shape[0])
+            self.raw_fetched.extend(int(first + b) for b in zero)
+        return packed, sizes_h, crc, raw
+
+    def push_remainder(self, d: int, n_files: int, data: np.ndarray):
+        """host bytes that precede file d's next device text: they join its (empty) remainder."""
+        torch = self.torch
+        while len(self.rem) < n_files:
+            self.rem.append(torch.empty(0, dtype=torch.uint8, device=self.dev))
+        if int(self.rem[d].numel()):
+            raise RuntimeError("GpuBgzf.push_remainder: file %d has a device remainder already" % d)
+        with torch.cuda.stream(self.stream):
+            self.rem[d] = torch.from_numpy(np.ascontiguousarray(data).copy()).to(self.dev)
+
+    def take_remainders(self):
+        """the files' remainders brought to the host (uint8 arrays), the device's emptied: what a
+        flush or the close appends to the sinks (bsdc_bgzf_sink_append)."""
+        torch = self.torch
+        if self.job is not None:
+            raise RuntimeError("GpuBgzf.take_remainders with a job in flight")
+        with torch.cuda.stream(self.stream):
+            host = [r.to("cpu", non_blocking=False).numpy() for r in self.rem]
+        self.rem = [torch.empty(0, dtype=torch.uint8, device=self.dev) for _ in self.rem]
+        return host
+
+    def counters(self) -> dict:
+        return {"blocks": self.blocks, "text_bytes": self.bytes_in, "compressed_bytes": self.bytes_out,
+                "fallback_blocks": self.fallback_blocks}
 
     def compress(self, data_ptr: int, nbytes: int):
         """host bytes [data_ptr, +nbytes) (whole blocks) -> (packed blocks, sizes int32[nblk])."""
@@ -978,14 +1135,19 @@ class _BgzfWriter:
             return
         nb, crc, raw = self.pending
         self.pending = None
-        packed, sizes = self.gpu.finish()
+        if crc is None:  # (a job of add_device: the CRCs come from the GPU, raw bytes only for blocks handed back)
+            packed, sizes, crc, raw = self.gpu.finish_device()
+            raw_ptr = raw.ctypes.data if raw is not None else None
+        else:
+            packed, sizes = self.gpu.finish()
+            raw_ptr = raw.data_ptr()
         b = off = 0  # the blocks / packed bytes of the sinks before this one
         for sink, n in zip(self.sinks, nb):
             if n == 0:
                 continue
             sz = np.ascontiguousarray(sizes[b:b + n])
             if self.lib.bsdc_bgzf_sink_put(sink, n, packed.ctypes.data + off, _ptr(sz), crc.ctypes.data + 4 * b,
-                                           raw.data_ptr() + b * 65280, int(threads)) != 0:
+                                           None if raw_ptr is None else raw_ptr + b * 65280, int(threads)) != 0:
                 raise self._err()
             off += int(np.maximum(sz, 0).sum(dtype=np.int64))
             b += n
@@ -1084,9 +1246,49 @@ class FastqWriter(_BgzfWriter):
         if fragment and self.lib.bsdc_fastq_writer_fragment(self.h) != 0:  # (no EOF blocks: ranks.assemble)
             raise self._err()
 
+    def add_device(self, pieces, threads: int = 0):
+        """Text that bsdc_fastq_format left in HBM joins the pair: pieces[d] = file d's byte ranges
+        (GpuBgzf.submit_device).  The protocol of add on the GPU path without encode and take: the
+        job before is written, this one submitted; its whole blocks come back compressed with their
+        CRC32s, the remainders stay on the device until a flush, the close or a host add."""
+        if self.gpu is None:
+            raise ValueError("FastqWriter.add_device needs a GpuBgzf")
+        self._drain(threads)
+        # host text added before (add) left its remainder in the sinks' tails: it goes in front of
+        # this text, as the device remainder (which add has emptied), so the bytes stay in order
+        for d, sink in enumerate(self.sinks):
+            tail = np.empty(65536, np.uint8)
+            n = int(self.lib.bsdc_bgzf_sink_take_tail(sink, _ptr(tail), tail.shape[0]))
+            if n < 0:
+                raise self._err()
+            if n:
+                self.gpu.push_remainder(d, len(self.sinks), tail[:n])
+        self.pending = (self.gpu.submit_device(pieces), None, None)
+
+    def _remainders(self, threads: int):
+        """the device remainders (< 65280 bytes each) brought to the sinks' tails"""
+        if self.gpu is None or not any(int(r.numel()) for r in getattr(self.gpu, "rem", ())):
+            return  # (no device text was added, or the compressor is a stand-in without that path)
+        self._drain(threads)
+        for sink, r in zip(self.sinks, self.gpu.take_remainders()):
+            if r.shape[0] and self.lib.bsdc_bgzf_sink_append(sink, _ptr(r), int(r.shape[0])) != 0:
+                raise self._err()
+
+    def add(self, recs: OutRecordsBam, threads: int = 0):
+        self._remainders(threads)  # (host text after device text: in order)
+        super().add(recs, threads)
+
     def flush(self, threads: int = 0) -> Tuple[int, int]:
         """Everything added so far written as whole BGZF blocks; -> (length of file 1, of file 2)."""
+        self._remainders(threads)
         return self._flush(threads)
+
+    def close(self, threads: int = 0):
+        try:
+            if self.h:
+                self._remainders(threads)
+        finally:
+            super().close(threads)
 
 
 def read_fasta(path: str, header: BamHeader) -> R.Reference:

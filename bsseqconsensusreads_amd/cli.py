@@ -57,6 +57,9 @@ def parse(argv):
                        help="deflate the output BAM's and FASTQ pair's blocks on the GPU (streaming; files ~4%% larger)")
         p.add_argument("--gpu-inflate", default="false", choices=("true", "false"),
                        help="inflate the input BAM's BGZF blocks on the GPU (streaming, --gpus 1; the same output)")
+        p.add_argument("--gpu-fastq", default="false", choices=("true", "false"),
+                       help="format, checksum and deflate the FASTQ pair on the GPU (streaming, --gpus 1; needs "
+                            "--fastq1/--fastq2; the files of a --gpu-bgzf run)")
         p.add_argument("--batch-bases", type=int, default=None, help="device batch budget in bases")
         p.add_argument("--chunk-mb", type=int, default=64, help="--stream: record MiB per chunk")
         if name == "step5":
@@ -108,6 +111,13 @@ def parse(argv):
         ap.error("nothing to write: give OUT.bam or --fastq1/--fastq2")
     if a.gpu_inflate == "true" and getattr(a, "gpus", 1) > 1:
         ap.error("--gpu-inflate is not supported with --gpus %d yet (the rank processes start without torch)" % a.gpus)
+    if a.gpu_fastq == "true":
+        if a.fastq1 is None:
+            ap.error("--gpu-fastq needs --fastq1/--fastq2")
+        if getattr(a, "gpus", 1) > 1:
+            ap.error("--gpu-fastq is not supported with --gpus %d yet (one process, one GPU)" % a.gpus)
+        if a.stream == "false":
+            ap.error("--gpu-fastq applies to the streaming step only: not with --stream false")
     if a.gpu_inflate == "true" and a.stream == "false":
         print("warning: --gpu-inflate applies to the streaming step only; --stream false inflates on the host",
               file=sys.stderr)
@@ -208,7 +218,10 @@ def main(argv=None) -> int:
                 info = bam.step5_stream(a.input, a.reference, out, eng, a.read_name_prefix, a.threads, a.compression,
                                         fq, tags=a.output_per_base_tags == "true", chunk_bytes=a.chunk_mb << 20,
                                         batch_bases=a.batch_bases, gpu_bgzf=a.gpu_bgzf == "true", filter=flt,
-                                        gpu_inflate=a.gpu_inflate == "true")
+                                        gpu_inflate=a.gpu_inflate == "true", gpu_fastq=a.gpu_fastq == "true")
+            elif a.cmd == "step5" and a.gpu_fastq == "true":
+                raise ValueError("--gpu-fastq applies to the streaming step only: %s is not coordinate-sorted "
+                                 "and would be read whole" % a.input)
             elif a.cmd == "step5":
                 info = bam.step5(a.input, a.reference, out, eng, a.read_name_prefix, a.threads, a.compression, fq,
                                  tags=a.output_per_base_tags == "true", batch_bases=a.batch_bases, dist=dist,
@@ -218,7 +231,7 @@ def main(argv=None) -> int:
                                             tags=a.output_per_base_tags == "true", chunk_bytes=a.chunk_mb << 20,
                                             batch_bases=a.batch_bases, gpu_bgzf=a.gpu_bgzf == "true",
                                             min_consensus_base_quality=a.min_consensus_base_quality, filter=flt,
-                                            gpu_inflate=a.gpu_inflate == "true")
+                                            gpu_inflate=a.gpu_inflate == "true", gpu_fastq=a.gpu_fastq == "true")
             else:
                 info = bam.molecular(a.input, out, eng, a.read_name_prefix, a.threads, a.compression, fq,
                                      tags=a.output_per_base_tags == "true",

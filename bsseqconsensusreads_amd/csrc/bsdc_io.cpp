@@ -2339,6 +2339,19 @@ int32_t bsdc_bgzf_sink_put(bsdc_bgzf_sink *s, int64_t nblk, uint8_t *packed, con
     return s->put(nblk, packed, sizes, crc, raw);
 }
 int64_t bsdc_bgzf_sink_tell(bsdc_bgzf_sink *s) { return s->tell(); }
+int32_t bsdc_bgzf_sink_append(bsdc_bgzf_sink *s, const uint8_t *bytes, int64_t n) {
+    if (!s || n < 0 || (n > 0 && !bytes)) return fail(BSDC_IO_EFORMAT, "bad bytes to append to a BGZF sink");
+    s->tail.insert(s->tail.end(), bytes, bytes + n);
+    return 0;
+}
+int64_t bsdc_bgzf_sink_take_tail(bsdc_bgzf_sink *s, uint8_t *dst, int64_t cap) {
+    if (!s || cap < 0 || (cap > 0 && !dst)) return fail(BSDC_IO_EFORMAT, "bad buffer for a BGZF sink's tail");
+    const int64_t n = (int64_t)s->tail.size();
+    if (n > cap) return fail(BSDC_IO_EFORMAT, "a BGZF sink's tail is larger than the buffer");
+    if (n) memcpy(dst, s->tail.data(), (size_t)n);
+    s->tail.clear();
+    return n;
+}
 }  // extern "C"
 
 namespace {

@@ -52,6 +52,22 @@ def _dptr(t: torch.Tensor) -> int:
     return int(t.data_ptr())
 
 
+@dataclass
+class FastqText:
+    """What Engine.fastq leaves on a DeviceBatch: the FASTQ text of its kept families in HBM
+    (bsdc_fastq_format).  text[d]: file d's bytes (uint8, `cap[d]` of them allocated); off: int64
+    [2, F + 1] on the device, the families' byte offsets per file, off[d, F] = the text's size;
+    event: recorded after the launch; name_off: the host copy of the names' offsets (what
+    bam.fastq_offsets takes).  Dropping the object releases the text."""
+
+    text: tuple
+    off: torch.Tensor
+    cap: tuple
+    event: "torch.cuda.Event"
+    name_off: np.ndarray
+    total: Optional[tuple] = None  # (file 1's bytes, file 2's), once fetched
+
+
 class DeviceBatch:
     """A FamilyBatch resident in HBM plus its output buffers."""
 
@@ -99,6 +115,7 @@ class DeviceBatch:
                 self.t["ss_wide"] = torch.from_numpy(self.ss_wide.view(np.uint8)).to(device)
                 self.ss_wdepth = torch.zeros(nw, dtype=torch.int16, device=device)
                 self.ss_werr = torch.zeros(nw, dtype=torch.int16, device=device)
+        self.fastq: Optional[FastqText] = None  # Engine.fastq
         self.filt = self.masked = None
         if filt:  # bsdc_filter's outputs: reason bits per family, newly masked columns per end
             self.filt = torch.zeros(max(F, 1), dtype=torch.uint8, device=device)
@@ -150,14 +167,21 @@ class DeviceBatch:
         return (self.status[:F].cpu().numpy(),
                 self.len[:2 * F].cpu().numpy().view(np.uint16).astype(np.int32).reshape(F, 2))
 
-    def fetch(self, alloc=None, ss: bool = True):
+    def fetch(self, alloc=None, ss: bool = True, seqqual: bool = True):
         """-> dict of numpy arrays (consensus and, if dumped, the post-tool records; after
         Engine.filter also "filt" [F] and "masked" [F, 2]).  ss=False leaves the single-strand rows
-        of a tags batch in HBM (a filtered output without consensus tags).  The copies
+        of a tags batch in HBM (a filtered output without consensus tags).  seqqual=False (after
+        Engine.fastq, when no BAM is written): "status", "len", ("filt", "masked") and "fastq_total"
+        (the two texts' sizes, checked against the buffers) only -- the bases and qualities stay
+        in HBM, where the text was made of them; `ss` does not apply and `alloc` is refused.  The copies
         are queued together on the current stream into pinned host memory (torch's caching host
         allocator), then one synchronize.  With alloc(nbytes) -> uint8 array (a fleet worker's
         shared segment) the outputs land in that buffer instead, so they leave the worker by name."""
         F = self.n_fam
+        if not seqqual:
+            if alloc is not None:
+                raise ValueError("fetch(seqqual=False) copies into pinned memory only: no alloc")
+            return self._fetch_small()
         t = {"status": self.status[:F], "len": self.len[:2 * F], "seq": self.seq[:F * self.stride],
              "qual": self.qual[:2 * F * self.stride]}
         n = 4 * F * self.stride
@@ -216,6 +240,25 @@ class DeviceBatch:
             out["dump_tags"] = a["dump_tags"]
             out["dump_seq"] = a["dump_seq"]
             out["dump_qual"] = a["dump_qual"]
+        return out
+
+    def _fetch_small(self):
+        F = self.n_fam
+        if self.fastq is None:
+            raise ValueError("fetch(seqqual=False) needs Engine.fastq on the batch first")
+        t = {"status": self.status[:F], "len": self.len[:2 * F], "fastq_total": self.fastq.off[:, F].contiguous()}
+        if self.filt is not None:
+            t.update(filt=self.filt[:F], masked=self.masked[:2 * F])
+        h = {k: v.to("cpu", non_blocking=True) for k, v in t.items()}
+        torch.cuda.current_stream(self.device).synchronize()
+        out = {"status": h["status"].numpy(), "len": h["len"].numpy().view(np.uint16).astype(np.int32).reshape(F, 2),
+               "stride": self.stride}
+        if self.filt is not None:
+            out["filt"] = h["filt"].numpy()
+            out["masked"] = h["masked"].numpy().view(np.uint16).astype(np.int32).reshape(F, 2)
+        self.fastq.total = out["fastq_total"] = tuple(int(x) for x in h["fastq_total"].numpy())
+        for d in range(2):
+            assert 0 <= self.fastq.total[d] <= self.fastq.cap[d], (self.fastq.total, self.fastq.cap)
         return out
 
 
@@ -356,6 +399,40 @@ class Engine:
         rc = self.lib.bsdc_filter(self.ctx, C.byref(p), 1 if molecular else 0, db.n_fam, C.byref(db._o),
                                   C.c_void_p(_dptr(db.filt)), C.c_void_p(_dptr(db.masked)), C.c_void_p(s.cuda_stream))
         self._check(rc, "bsdc_filter")
+
+    def fastq(self, db: DeviceBatch, names, stream: Optional[torch.cuda.Stream] = None) -> FastqText:
+        """The FASTQ text of the batch's kept families formatted where the consensus lies
+        (bsdc_fastq_format), enqueued on the stream that ran the vote, after it and after `filter`.
+        names: the families' read names, one each, as a packed table (.buf, .off: bam.family_names).
+        The table goes up, two text buffers of the size known beforehand (bsdc_fastq_text_bound)
+        are allocated, and db.fastq holds them with an event recorded behind the launch."""
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        F = db.n_fam
+        off_h = np.ascontiguousarray(names.off, np.int64)
+        if off_h.shape[0] != F + 1:
+            raise ValueError("one name per family: %d offsets for %d families" % (off_h.shape[0], F))
+        off_h = off_h - off_h[0]
+        nb = int(off_h[-1])
+        buf_h = np.ascontiguousarray(names.buf[int(names.off[0]):int(names.off[0]) + nb], np.uint8)
+        cap = int(self.lib.bsdc_fastq_text_bound(F, nb, db.stride))
+        with torch.cuda.device(self.device), torch.cuda.stream(s):
+            d_off = torch.from_numpy(off_h).to(self.device)
+            d_buf = torch.from_numpy(buf_h if nb else np.zeros(1, np.uint8)).to(self.device)
+            text = tuple(torch.empty(max(cap, 16), dtype=torch.uint8, device=self.device) for _ in range(2))
+            off = torch.empty((2, F + 1), dtype=torch.int64, device=self.device)
+            tmp = torch.empty(int(self.lib.bsdc_fastq_tmp_bytes(F)), dtype=torch.uint8, device=self.device)
+            rc = self.lib.bsdc_fastq_format(C.byref(db._o), C.c_void_p(_dptr(db.filt)) if db.filt is not None else None,
+                                            F, C.c_void_p(_dptr(d_off)), C.c_void_p(_dptr(d_buf)),
+                                            C.c_void_p(off_h.ctypes.data), C.c_void_p(_dptr(off[0])),
+                                            C.c_void_p(_dptr(off[1])), C.c_void_p(_dptr(text[0])),
+                                            C.c_void_p(_dptr(text[1])), cap, cap, C.c_void_p(_dptr(tmp)),
+                                            C.c_void_p(s.cuda_stream))
+            if rc != 0:
+                raise RuntimeError("bsdc_fastq_format failed (%d)" % rc)
+            ev = torch.cuda.Event()
+            ev.record(s)
+        db.fastq = FastqText(text, off, (cap, cap), ev, off_h)
+        return db.fastq
 
     def tables(self):
         lr = np.zeros(256, np.int64)

@@ -82,6 +82,27 @@ class Consensus:
     # pairs that go out are those with status & 1 and filt == 0 (filter.kept)
     filt: Optional[np.ndarray] = None
     masked: Optional[np.ndarray] = None
+    # with run_batches(fastq_names=...): one FastqPiece per batch, the kept families' FASTQ text in
+    # HBM (Engine.fastq); seq / qual are then empty ([F, 2, 0]) when they were left on the device
+    fastq: Optional[list] = None
+
+
+@dataclass
+class FastqPiece:
+    """One batch's FASTQ text on the device and where its kept families lie in it: text = the two
+    files' uint8 device tensors, event = recorded behind the launch, kept = the batch's kept
+    families, koff[d] int64 [kept + 1] = the byte offset of each kept family in file d's text
+    (bam.fastq_offsets at the kept families; the last one = the text's size, checked against the
+    device's total).  Dropping it releases the text."""
+
+    text: tuple
+    event: object
+    kept: int
+    koff: tuple
+
+    def ranges(self, a: int, b: int) -> list:
+        """kept families a..b-1 as submit_device pieces, one list per file."""
+        return [[(self.text[d], int(self.koff[d][a]), int(self.koff[d][b]), self.event)] for d in range(2)]
 
 
 def _stripped_cigar(raw: R.RawRecords, k: int, strip: bool) -> List[int]:
@@ -233,6 +254,10 @@ def consensus_from_output(fb: FamilyBatch, out: dict) -> Consensus:
     F = fb.n_fam
     stride = out["stride"]
     from .bam import unpack_nibbles
+    if "seq" not in out:  # fetch(seqqual=False): the bases stayed in HBM
+        return Consensus(fb.fam_mi.copy(), out["status"], out["len"], np.zeros((F, 2, 0), np.uint8),
+                         np.zeros((F, 2, 0), np.uint8), fb.fam_off.astype(np.int64), fb.src.astype(np.int64), None,
+                         out.get("filt"), out.get("masked"))
     seq = unpack_nibbles(out["seq"].reshape(F, 2, stride // 2))
     ss = None
     if "ss_len" in out:
@@ -279,12 +304,15 @@ def materialize_ranges(plan: FamilyPlan, ranges, images=None) -> List[FamilyBatc
 
 def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
                 timing: Optional[dict] = None, filter: Optional[FilterParams] = None,
-                molecular: bool = False) -> List[Consensus]:
+                molecular: bool = False, fastq_names=None, seqqual: bool = True) -> List[Consensus]:
     """Materialized batches (any iterable, taken one at a time) through the kernels, one launch
     each, output per batch in order; a batch uploads and launches before the one before it is
     fetched.  `timing`: seconds added per host step (upload, fetch = wait + copy out, unpack).
     `filter`: each batch is filtered on the device after its vote (Engine.filter; `molecular`:
-    step-1 records), which needs the tags' rows there; they are copied out only with `tags`."""
+    step-1 records), which needs the tags' rows there; they are copied out only with `tags`.
+    `fastq_names` (batch -> its families' read names, a packed table): each batch's FASTQ text is
+    formatted on the device right after its vote or filter (Engine.fastq) and its Consensus carries
+    the handle (Consensus.fastq); seqqual=False then leaves the bases and qualities in HBM."""
     import time
     T = timing if timing is not None else {}
     parts: List[Consensus] = []
@@ -292,9 +320,11 @@ def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
 
     def out(fb, db):
         t0 = time.perf_counter()
-        o = db.fetch(ss=tags)
+        o = db.fetch(ss=tags) if seqqual or db.fastq is None else db.fetch(seqqual=False)
         t1 = time.perf_counter()
         parts.append(consensus_from_output(fb, o))
+        if db.fastq is not None:
+            parts[-1].fastq = [_fastq_piece(db, parts[-1])]
         T["fetch"] = T.get("fetch", 0.0) + t1 - t0
         T["unpack"] = T.get("unpack", 0.0) + time.perf_counter() - t1
     for fb in batches:
@@ -303,6 +333,8 @@ def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
         engine.run(db, mode | (MODE_TAGS if db.tags else 0))
         if filter is not None:
             engine.filter(db, filter, molecular)
+        if fastq_names is not None:
+            engine.fastq(db, fastq_names(fb))
         T["upload"] = T.get("upload", 0.0) + time.perf_counter() - t0
         if prev is not None:
             out(*prev)
@@ -312,11 +344,29 @@ def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
     return parts
 
 
+def _fastq_piece(db, cons: Consensus) -> FastqPiece:
+    """The batch's device text as a FastqPiece: host offsets from the fetched lengths, their totals
+    checked against the device's (a stream synchronised by the fetch before)."""
+    from .bam import fastq_offsets
+    from .filter import kept
+    fq = db.fastq
+    if fq.total is None:
+        fq.total = tuple(int(x) for x in fq.off[:, db.n_fam].cpu().numpy())
+    off = fastq_offsets(cons.status, cons.length, cons.filt, fq.name_off)
+    if (int(off[0][-1]), int(off[1][-1])) != tuple(fq.total) or max(fq.total) > min(fq.cap):
+        raise RuntimeError("FASTQ text: the device wrote %r bytes, the host counts %r (buffers %r)" % (
+            fq.total, (int(off[0][-1]), int(off[1][-1])), fq.cap))
+    k = np.nonzero(kept(cons))[0]
+    koff = tuple(np.concatenate([o[k], o[-1:]]) for o in off)
+    return FastqPiece(fq.text, fq.event, int(k.shape[0]), koff)
+
+
 def concat_consensus(parts: List[Consensus]) -> Consensus:
     """Consensus of consecutive family ranges -> one Consensus in range order (strides padded to
     the widest)."""
     if len(parts) == 1:
         return parts[0]
+    fastq = [x for p in parts for x in p.fastq] if parts and all(p.fastq is not None for p in parts) else None
     if not parts:
         z = np.zeros(0, np.int32)
         return Consensus(z, np.zeros(0, np.uint8), np.zeros((0, 2), np.int32), np.zeros((0, 2, 16), np.uint8),
@@ -351,7 +401,7 @@ def concat_consensus(parts: List[Consensus]) -> Consensus:
     return Consensus(np.concatenate([p.fam_mi for p in parts]), np.concatenate([p.status for p in parts]),
                      np.concatenate([p.length for p in parts]), np.concatenate([pad(p.seq) for p in parts]),
                      np.concatenate([pad(p.qual) for p in parts]), fro.astype(np.int64),
-                     np.concatenate([np.asarray(p.fam_src, np.int64) for p in parts]), ss, filt, masked)
+                     np.concatenate([np.asarray(p.fam_src, np.int64) for p in parts]), ss, filt, masked, fastq)
 
 
 def _tools_batched(engine: Engine, raw: R.RawRecords, batch_bases: Optional[int]) -> OutRecords:

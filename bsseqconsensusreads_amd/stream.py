@@ -46,7 +46,10 @@ class StreamJob:
     piece keyed (pair, MINKEY)): a rank does not register cross keys (bsdc_io.cpp), so the deferred
     families of a contig's cross keys go between those pieces.
     gpu_inflate: the input BAM's BGZF blocks are inflated on the engine's GPU (bam.GpuInflate; the
-    same bytes, so the same output files); an Engine stream only."""
+    same bytes, so the same output files); an Engine stream only.
+    gpu_fastq: the FASTQ pair's text is formatted, checksummed and deflated on the engine's GPU
+    (Engine.fastq, bam.GpuBgzf.submit_device): the files of a gpu_bgzf run, byte for byte; needs
+    `fastq`, an Engine stream only."""
 
     in_bam: str
     fasta: Optional[str]
@@ -71,7 +74,8 @@ class StreamJob:
     late_splices: Optional[np.ndarray] = None
     first_key: Optional[tuple] = None
     regions: bool = False
-    gpu_inflate: bool = False
+    gpu_fastq: bool = False
+    gpu_inflate: bool = False  # (stays the last field)
 
 
 @dataclasses.dataclass
@@ -278,15 +282,22 @@ class BackEnd(_Stages):
     and a piece with that key starts there, noted in `marks` ((BAM offset, FASTQ offsets x 2), sort
     key (key, tie)); the first mark is the header's, keyed first_key.  Once a chunk is written its
     pooled buffers go back to `bufs` and on_written(chunk) is called.  Leaving the `with` block
-    ends the threads; a failing writer closes its files quietly (bam.close_quietly)."""
+    ends the threads; a failing writer closes its files quietly (bam.close_quietly).
+    fq_device (a call that gives the device): the FASTQ pair takes a chunk's text from HBM where
+    its Consensus carries it (Consensus.fastq, pipeline.FastqPiece): the cuts become byte ranges of
+    that text (FastqWriter.add_device), no records are built without a BAM, and the text is
+    released once the chunk is written.  A chunk without device text (a split_ext plan) goes the
+    host way through the same writer.  fastq_counters: the pair's GpuBgzf counters at the close."""
 
     def __init__(self, fault: Fault, out_bam: Optional[str], fastq, header, prefix: str, threads: int, level: int,
                  bufs: "bam.BufferPool", molecular: bool = False, gz_device=None, fragment: Optional[str] = None,
-                 marks: Optional[list] = None, first_key=(MINKEY, 0, 1), tie: int = 1, on_written=None):
+                 marks: Optional[list] = None, first_key=(MINKEY, 0, 1), tie: int = 1, on_written=None,
+                 fq_device=None):
         self.fault, self.out_bam, self.fastq, self.header, self.prefix = fault, out_bam, fastq, header, prefix
         self.threads, self.level, self.bufs, self.molecular, self.gz_device = threads, level, bufs, molecular, gz_device
         self.fragment, self.first_key, self.tie, self.on_written = fragment, first_key, tie, on_written
         self.marks = [] if marks is None else marks
+        self.fq_device, self.fastq_counters = fq_device, None
         self.T = {"records": 0.0, "encode": 0.0, "writer_wait": 0.0}
         self.records_out = 0
         self.outs, self.recq = queue.Queue(maxsize=1), queue.Queue(maxsize=1)  # consensus -> builder -> writer
@@ -306,12 +317,16 @@ class BackEnd(_Stages):
                     break
                 cons, chunk, cuts = item
                 t0 = time.perf_counter()
-                recs, tags_buf = bam.duplex_records(cons, chunk.raw, self.prefix, self.threads,
-                                                    molecular=self.molecular, pool=self.bufs)
+                text = cons.fastq if self.fq_device is not None else None
+                if text is not None and self.out_bam is None:  # (the FASTQ pair reads no records)
+                    recs, tags_buf = None, None
+                else:
+                    recs, tags_buf = bam.duplex_records(cons, chunk.raw, self.prefix, self.threads,
+                                                        molecular=self.molecular, pool=self.bufs)
                 self.T["records"] += time.perf_counter() - t0
                 chunk.raw = chunk.plan = chunk.batches = None
                 del item, cons
-                self.recq.put((recs, tags_buf, chunk, cuts))
+                self.recq.put((recs, tags_buf, chunk, cuts, text))
         except BaseException as e:  # noqa: BLE001
             self.fault(e)
             while self.outs.get() is not None:  # drain so that put() never blocks
@@ -327,30 +342,37 @@ class BackEnd(_Stages):
             if self.out_bam is not None:  # (a GpuBgzf each: one job in flight)
                 w = bam.BamWriter(self.out_bam, bam.output_header(self.header), self.level, gz(), self.fragment)
             if self.fastq is not None:
-                fq = bam.FastqWriter(self.fastq[0], self.fastq[1], self.level, gz(), self.fragment is not None)
+                fq = bam.FastqWriter(self.fastq[0], self.fastq[1], self.level,
+                                     bam.GpuBgzf(self.fq_device()) if self.fq_device is not None else gz(),
+                                     self.fragment is not None)
             self.marks.append(((0, 0, 0), self.first_key))  # (a first piece holds the header, if any)
             while True:
                 item = self.recq.get()
                 if item is None:
                     break
-                recs, tags_buf, chunk, cuts = item
+                recs, tags_buf, chunk, cuts, text = item
                 t1 = time.perf_counter()
                 a = 0
-                for idx, key in cuts + [(recs.n, None)]:
-                    part = recs if (a == 0 and idx == recs.n) else _slice_records(recs, a, idx)
+                n_out = recs.n if recs is not None else 2 * sum(x.kept for x in text)
+                part = None
+                for idx, key in cuts + [(n_out, None)]:
+                    if recs is not None:
+                        part = recs if (a == 0 and idx == n_out) else _slice_records(recs, a, idx)
                     if idx > a:
                         if w is not None:
                             w.add(part, th)
-                        if fq is not None:
+                        if fq is not None and text is not None:
+                            fq.add_device(_text_ranges(text, a // 2, idx // 2), th)
+                        elif fq is not None:
                             fq.add(part, th)
                     if key is not None:  # everything so far leaves as whole blocks; a piece starts here
                         bo = w.flush(th) if w is not None else 0
                         fo = fq.flush(th) if fq is not None else (0, 0)
                         self.marks.append(((bo, fo[0], fo[1]), (key[0], key[1], self.tie)))
                     a = idx
-                self.records_out += recs.n
+                self.records_out += n_out
                 self.T["encode"] += time.perf_counter() - t1
-                del item, recs, part
+                del item, recs, part, text  # (the device text is released here, the job that reads it submitted)
                 # (the chunk's records are written; nothing refers to their arrays)
                 self.bufs.give(chunk.pool_buf)
                 self.bufs.give(tags_buf)
@@ -360,6 +382,8 @@ class BackEnd(_Stages):
                 w.close(th)
             if fq is not None:
                 fq.close(th)
+                if self.fq_device is not None:
+                    self.fastq_counters = fq.gpu.counters()
         except BaseException as e:  # noqa: BLE001
             self.fault(e)
             bam.close_quietly(w, fq)
@@ -378,12 +402,14 @@ def step5_stream(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, p
                  threads: int = 0, level: int = 6, fastq: Optional[Tuple[str, str]] = None, tags: bool = True,
                  chunk_bytes: int = bam.DEFAULT_CHUNK_BYTES, slack: int = bam.DEFAULT_SLACK,
                  batch_bases: Optional[int] = None, stats: Optional[dict] = None, gpu_bgzf: bool = False,
-                 defer: Optional[int] = None, read_size: int = 8 << 20, filter=None, gpu_inflate: bool = False) -> dict:
+                 defer: Optional[int] = None, read_size: int = 8 << 20, filter=None, gpu_inflate: bool = False,
+                 gpu_fastq: bool = False) -> dict:
     """step5 in bounded memory, pipelined (run); defer: the span past which a template is
     deferred (default DEFAULT_DEFER_SPAN; 0 = off); read_size: compressed bytes per refill;
-    filter: as step5's; gpu_inflate: the input's BGZF blocks inflate on the GPU (bam.GpuInflate)."""
+    filter: as step5's; gpu_inflate: the input's BGZF blocks inflate on the GPU (bam.GpuInflate);
+    gpu_fastq: the FASTQ pair is formatted, checksummed and deflated on the GPU (StreamJob)."""
     job = StreamJob(in_bam, fasta, out_bam, fastq, prefix, threads, level, tags, gpu_bgzf, chunk_bytes, slack,
-                    batch_bases, read_size, filter=filter, defer=defer, gpu_inflate=gpu_inflate)
+                    batch_bases, read_size, filter=filter, defer=defer, gpu_inflate=gpu_inflate, gpu_fastq=gpu_fastq)
     return _public(run(job, engine, stats=stats))
 
 
@@ -391,7 +417,7 @@ def molecular_stream(in_bam: str, out_bam: Optional[str], engine=None, prefix: O
                      level: int = 6, fastq: Optional[Tuple[str, str]] = None, tags: bool = True,
                      chunk_bytes: int = bam.DEFAULT_CHUNK_BYTES, batch_bases: Optional[int] = None,
                      stats: Optional[dict] = None, gpu_bgzf: bool = False, min_consensus_base_quality: int = 0,
-                     filter=None, gpu_inflate: bool = False) -> dict:
+                     filter=None, gpu_inflate: bool = False, gpu_fastq: bool = False) -> dict:
     """Rule call_consensus_reads_molecular (main.snake.py:46-55) in bounded memory: the same
     pipeline as step5_stream over a GroupReadsByUmi-ordered input cut between MI runs
     (stream_chunks(runs=True)); each chunk's runs are its consensus families (pipeline.molecular_records,
@@ -400,7 +426,7 @@ def molecular_stream(in_bam: str, out_bam: Optional[str], engine=None, prefix: O
     (main.snake.py:54, README.md:83); this holds about six chunks."""
     job = StreamJob(in_bam, None, out_bam, fastq, prefix, threads, level, tags, gpu_bgzf, chunk_bytes,
                     batch_bases=batch_bases, molecular=int(min_consensus_base_quality), filter=filter,
-                    gpu_inflate=gpu_inflate)
+                    gpu_inflate=gpu_inflate, gpu_fastq=gpu_fastq)
     return _public(run(job, engine, stats=stats))
 
 
@@ -456,6 +482,19 @@ def _region_cuts(cons, raw, plan, prev: int):
     before[0] = prev
     before[1:] = k0[:-1]
     return [(2 * int(em[f]), (int(k0[f]), MINKEY)) for f in np.nonzero(k0 != before)[0]], int(k0[-1])
+
+
+def _text_ranges(text, a: int, b: int) -> list:
+    """Kept families a..b-1 of a chunk whose batches' device text is `text` (pipeline.FastqPiece
+    each, in order) -> FastqWriter.add_device's pieces: per file, the byte ranges in order."""
+    out, k0 = [[], []], 0
+    for x in text:
+        lo, hi = max(a - k0, 0), min(b - k0, x.kept)
+        if hi > lo:
+            for d, r in enumerate(x.ranges(lo, hi)):
+                out[d] += r
+        k0 += x.kept
+    return out
 
 
 def _slice_records(recs: "bam.OutRecordsBam", a: int, b: int) -> "bam.OutRecordsBam":
@@ -528,6 +567,10 @@ def _run_chunk(eng, runner, ch: Chunk, mode: int, tags: bool, job: StreamJob, G:
     if ch.batches is None:
         return pipeline.run_step5(eng, ch.raw, tags=tags, batch_bases=job.batch_bases, filter=job.filter)[0]
     fkw = {} if job.filter is None else {"filter": job.filter, "molecular": job.molecular is not None}
+    if job.gpu_fastq:  # the batches' FASTQ text is made where their consensus lies; no BAM: the bases stay there
+        raw = ch.raw
+        fkw.update(fastq_names=lambda fb: bam.family_names(fb.fam_mi, raw.mi_names, job.prefix),
+                   seqqual=job.out_bam is not None)
     return pipeline.concat_consensus(pipeline.run_batches(eng, ch.batches, mode, tags, G, **fkw))
 
 
@@ -556,8 +599,11 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
         eng = Engine(0) if own else engine
     else:
         eng = None
-        if job.gpu_bgzf or molecular or job.filter is not None or job.gpu_inflate:
-            raise ValueError("a runner stream: step 5 with host inflate and deflate only, unfiltered")
+        if job.gpu_bgzf or molecular or job.filter is not None or job.gpu_inflate or job.gpu_fastq:
+            raise ValueError("a runner stream: step 5 with host inflate and deflate only, unfiltered "
+                             "(no gpu_bgzf, gpu_inflate or gpu_fastq)")
+    if job.gpu_fastq and job.fastq is None:
+        raise ValueError("gpu_fastq needs the FASTQ pair (fastq=(path1, path2))")
     out_bam, fastq = job.out_bam, job.fastq
     info = {"records_in": 0, "families": 0, "families_emitted": 0, "records_out": 0, "chunks": 0,
             "spilled_bytes": 0, "deferred_families": 0, "splices": []}
@@ -607,13 +653,15 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
         back = BackEnd(fault, out_bam, fastq, header, prefix, job.threads, job.level, bufs, molecular,
                        (lambda: eng.device) if job.gpu_bgzf else None,
                        "first" if (solo and dspan) else job.fragment, marks, k_first,
-                       tie=0 if late is not None else 1)  # (a spill piece sorts before the stream's piece of its key)
+                       tie=0 if late is not None else 1,  # (a spill piece sorts before the stream's piece of its key)
+                       fq_device=(lambda: eng.device) if job.gpu_fastq else None)
+        pjob = dataclasses.replace(job, prefix=prefix)  # (the read names' prefix, resolved)
         mode = pipeline.MODE_VOTE if molecular else pipeline.MODE_CONVERT | pipeline.MODE_EXTEND | pipeline.MODE_VOTE
         tg = job.tags and out_bam is not None  # the FASTQ pair carries no tags
         with front, back:
             for ch in front:
                 t0 = time.perf_counter()
-                cons = _run_chunk(eng, runner, ch, mode, tg, job, G)
+                cons = _run_chunk(eng, runner, ch, mode, tg, pjob, G)
                 ch.batches = None
                 T["gpu"] += time.perf_counter() - t0
                 info["records_in"] += ch.raw.n
@@ -638,6 +686,8 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
             if inflater.error is not None:  # (the reader saw a failed call as a corrupt block)
                 fault.errors.insert(0, inflater.error)
         if not fault.errors:
+            if job.gpu_fastq:
+                info["gpu_fastq"] = back.fastq_counters
             info["records_out"] = back.records_out
             info["spilled_bytes"] = front.spilled_bytes
             info["deferred_families"] = int(rs.get("deferred", 0))
@@ -686,6 +736,8 @@ def _finish_deferred(job: StreamJob, eng, runner, marks, spill_path: str, info: 
                    eng, runner, marks=mk2)
         for k in ("records_in", "families", "families_emitted", "records_out"):
             info[k] += inf2[k]
+        if "gpu_fastq" in inf2:
+            info["gpu_fastq"] = {k: v + inf2["gpu_fastq"][k] for k, v in info["gpu_fastq"].items()}
         if "gpu_inflate" in inf2:  # (the spill's BAM, inflated the same way)
             info["gpu_inflate_deferred"] = inf2["gpu_inflate"]
         if job.filter is not None:

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BSDC_ABI_VERSION 17
+#define BSDC_ABI_VERSION 18
 #define BSDC_SMALL_BUCKETS 8
 #define BSDC_LARGE_BUCKETS 6
 #define BSDC_LARGE_LDS_MAX 158912 /* LDS arena bytes one large-family workgroup may use */ /* LDS arena size classes of the wavefront-per-family kernel */
@@ -326,6 +326,37 @@ int32_t bsdc_bgzf_inflate(const uint8_t *comp, int64_t n_comp, const bsdc_inflat
                           uint8_t *out, int64_t n_out, int32_t *status, void *stream);
 int32_t bsdc_bgzf_inflate_host(const uint8_t *comp, int64_t n_comp, const bsdc_inflate_block *blk, int64_t nblk,
                                uint8_t *out, int64_t n_out, int32_t *status);
+
+/* (ABI 18) The FASTQ pair formatted on the device (replaces picard SamToFastq behind the rules
+ * consensus_to_fq / consensusduplex_to_fq, main.snake.py:58-67,167-177, and the host writer's text
+ * pass; csrc/bsdc_fastq.hip): the text of a batch's kept families from the consensus where the vote
+ * left it.  `out` is the bsdc_consensus the vote filled (status, len, seq, qual, stride; qual 4-byte
+ * aligned) and filt the filter's output or NULL: family f is written when status[f] & 1 and (filt
+ * NULL or filt[f] == 0).  name_off [n_fam + 1] / name_buf: a packed table, one name per family (the
+ * "prefix:MI" of the BAM's records), at most 254 bytes each; name_off_host is the caller's host
+ * copy of name_off, which is what gets checked.  Per file d = 0 (first of pair), 1 (second):
+ * off_d [n_fam + 1] receives the exclusive prefix sum of the families' byte counts (off_d[n_fam] =
+ * the total) and text_d + off_d[f] the bytes of family f,
+ *   '@' name '/' ('1' | '2') '\n' SEQ '\n' '+' '\n' QUAL '\n'     (8 + name + 2 * len[2f + d] bytes)
+ * SEQ = row (f, d) of out->seq through "=ACMGRSVTWYHKDBN" (high nibble first), QUAL = (uint8_t)(33 + q).
+ * No byte at or past text_d + cap_d is written; the totals are true whatever the caps, so the
+ * caller compares.  bsdc_fastq_text_bound = a size known before the launch: the sum over the
+ * families of 8 + name length, plus 2 * n_fam * stride.  tmp: bsdc_fastq_tmp_bytes of 8-byte
+ * aligned scratch.  Sizes, scan and text are enqueued on `stream` (hipStream_t) by the one call,
+ * after the vote and the filter on it; device pointers but for `out` itself and name_off_host.
+ * BSDC_EINVAL: a NULL pointer (filt apart), a negative count or cap, a name outside 0..254 bytes. */
+int64_t bsdc_fastq_text_bound(int64_t n_fam, int64_t name_bytes, int32_t stride);
+int64_t bsdc_fastq_tmp_bytes(int64_t n_fam);
+int32_t bsdc_fastq_format(const bsdc_consensus *out, const uint8_t *filt, int64_t n_fam, const int64_t *name_off,
+                          const uint8_t *name_buf, const int64_t *name_off_host, int64_t *off0, int64_t *off1,
+                          uint8_t *text0, uint8_t *text1, int64_t cap0, int64_t cap1, uint8_t *tmp, void *stream);
+
+/* (ABI 18) The CRC32 (zlib / gzip) of whole BGZF blocks on the device (replaces the checksum pass of
+ * the gzip writer behind the same rules' F= / F2= outputs, main.snake.py:58-67,167-177):
+ * crc[blk0 + b] = the CRC32 of in[(blk0 + b) * 65280, + 65280) for b < nblk, one workgroup per
+ * block; what bsdc_bgzf_sink_put of libbsdc_io takes as the blocks' crc[].  A file's short last
+ * block stays with the host.  Device pointers, `in` 16-byte aligned; enqueued on `stream`. */
+int32_t bsdc_bgzf_crc32(const uint8_t *in, int64_t blk0, int64_t nblk, uint32_t *crc, void *stream);
 
 #ifdef __cplusplus
 }

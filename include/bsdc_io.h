@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define BSDC_IO_ABI_VERSION 14
+#define BSDC_IO_ABI_VERSION 15
 #define BSDC_IO_EFORMAT (-10) /* not BGZF/BAM, truncated, bad CRC */
 #define BSDC_IO_EIO (-11)     /* open/read/write failed */
 #define BSDC_IO_EINVAL (-22)  /* bad argument */
@@ -230,13 +230,23 @@ int32_t bsdc_bam_write(const char *path, const char *header_text, int64_t header
  * back, sizes[b] each with the CRC32 / ISIZE bytes still to fill (from crc[b]), 0 = deflate it
  * here from raw (what take copied) -- in order.  Takes and puts come in the same order.  tell =
  * the file's bytes written (after the writer's flush, a point where the file may be cut).  A sink
- * lives as long as its writer. */
+ * lives as long as its writer.
+ * (IO ABI 15) append puts n raw bytes at the end of the tail, as the writer's encode does with
+ * the text it formats: the remainder (< 65280 bytes per file) of a FASTQ text that libbsdc's
+ * bsdc_fastq_format made on the device and whose whole blocks went through put, brought back at a
+ * flush or the close, which then deflate it here as any tail (the gzip writer of picard SamToFastq
+ * behind main.snake.py:58-67,167-177).  take_tail is the way back: the whole tail (at most cap
+ * bytes, else an error) moves to dst and the count is returned -- the host text's remainder that
+ * device text follows, which the caller uploads behind nothing and in front of that text, so the
+ * file's bytes stay in order without a flush. */
 typedef struct bsdc_bgzf_sink bsdc_bgzf_sink;
 int64_t bsdc_bgzf_sink_whole(bsdc_bgzf_sink *s);
 int32_t bsdc_bgzf_sink_take(bsdc_bgzf_sink *s, int64_t nblk, uint8_t *dst, uint32_t *crc, int32_t n_threads);
 int32_t bsdc_bgzf_sink_put(bsdc_bgzf_sink *s, int64_t nblk, uint8_t *packed, const int32_t *sizes, const uint32_t *crc,
                            const uint8_t *raw, int32_t n_threads);
 int64_t bsdc_bgzf_sink_tell(bsdc_bgzf_sink *s);
+int32_t bsdc_bgzf_sink_append(bsdc_bgzf_sink *s, const uint8_t *bytes, int64_t n);
+int64_t bsdc_bgzf_sink_take_tail(bsdc_bgzf_sink *s, uint8_t *dst, int64_t cap);
 
 /* Streaming writer: the bytes bsdc_bam_write writes for all the records at once, written as
  * records are added (whole BGZF blocks deflated in parallel as they fill).  encode = add without

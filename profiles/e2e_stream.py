@@ -110,12 +110,14 @@ def child(args):
         info = bam.molecular(args.grouped, args.out, engine=eng, threads=args.threads, level=args.level)
     elif args.mode == "whole":
         info = bam.step5(args.inp, args.fa, args.out, engine=eng, threads=args.threads, level=args.level)
-    elif args.mode in ("stream_fastq", "stream_fastq_gpubgzf"):  # the fused FASTQ emission
-        # (main.snake.py:167-177), no BAM; _gpubgzf: its blocks deflated on the GPU
+    elif args.mode in ("stream_fastq", "stream_fastq_gpubgzf", "stream_fastq_gpufastq"):  # the fused FASTQ emission
+        # (main.snake.py:167-177), no BAM; _gpubgzf: its blocks deflated on the GPU; _gpufastq: its
+        # text formatted and checksummed there too
         info = bam.step5_stream(args.inp, args.fa, None, engine=eng, threads=args.threads, level=args.level,
                                 fastq=(args.out + ".1.fq.gz", args.out + ".2.fq.gz"),
                                 chunk_bytes=args.chunk_mb << 20, stats=stats,
-                                gpu_bgzf=args.mode == "stream_fastq_gpubgzf")
+                                gpu_bgzf=args.mode == "stream_fastq_gpubgzf",
+                                gpu_fastq=args.mode == "stream_fastq_gpufastq")
     else:  # stream, or stream_gpubgzf: the BAM's blocks deflated on the GPU (bam.GpuBgzf)
         info = bam.step5_stream(args.inp, args.fa, args.out, engine=eng, threads=args.threads, level=args.level,
                                 chunk_bytes=args.chunk_mb << 20, stats=stats, gpu_bgzf=args.mode == "stream_gpubgzf")
@@ -163,9 +165,10 @@ def main():
            "host_threads": a.threads, "level": a.level, "chunk_MiB": a.chunk_mb, "prep_s": round(prep, 1)}
     print("prepared", json.dumps(res), flush=True)
     outs = {}
-    for mode in a.modes.split(","):
+    for mode in a.modes.split(","):  # ("name@k": run k of a mode, for alternated repeats)
         out = os.path.join(d, mode + ".bam")
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", mode, "--inp", inp, "--fa", fa,
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", mode.split("@")[0], "--inp", inp,
+                            "--fa", fa,
                             "--out", out, "--threads", str(a.threads), "--chunk-mb", str(a.chunk_mb),
                             "--level", str(a.level), "--workers", str(a.workers), "--grouped", grouped],
                            stdout=subprocess.PIPE, text=True,
@@ -178,7 +181,7 @@ def main():
         res[mode] = r
         outs[mode] = out
         print(mode, json.dumps(r), flush=True)
-    bams = [open(outs[m], "rb").read() for m in outs if m != "stream_fastq" and "gpubgzf" not in m
+    bams = [open(outs[m], "rb").read() for m in outs if not m.startswith("stream_fastq") and "gpubgzf" not in m
             and not m.startswith("molecular") and not m.startswith("ranks")]
     if "ranks" in outs and "stream" in outs:  # other BGZF blocks at the rank seams: the bytes inside
         import gzip
@@ -199,6 +202,10 @@ def main():
         import gzip
         res["fastq_gpubgzf_text_identical"] = all(
             gzip.open(outs["stream_fastq"] + x).read() == gzip.open(outs["stream_fastq_gpubgzf"] + x).read()
+            for x in (".1.fq.gz", ".2.fq.gz"))
+    if "stream_fastq_gpufastq" in outs and "stream_fastq_gpubgzf" in outs:  # the same files
+        res["fastq_gpufastq_bytes_identical"] = all(
+            open(outs["stream_fastq_gpufastq"] + x, "rb").read() == open(outs["stream_fastq_gpubgzf"] + x, "rb").read()
             for x in (".1.fq.gz", ".2.fq.gz"))
     if "molecular_stream" in outs and "molecular_whole" in outs:  # GPU BGZF vs host deflate: the records
         sys.path.insert(0, ROOT)
