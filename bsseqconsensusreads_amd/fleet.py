@@ -727,7 +727,7 @@ def step5_stream_multi(in_bam: str, fasta: str, out_bam: Optional[str], devices:
     front end and back end (stream.FrontEnd, stream.BackEnd) with the dealer and the collector
     between them instead of a GPU stage.  Same file contract and output bytes as bam.step5 /
     bam.step5_stream (main.snake.py:121-164).
-    gpu_bgzf: the writer deflates on devices[0] (bam.GpuBgzf; the coordinator touches that GPU
+    gpu_bgzf: the writer deflates on devices[0] (bgzf.GpuBgzf; the coordinator touches that GPU
     only after its workers are spawned).  fleet: an already started Fleet over `devices` (left
     running; e.g. to time the stream without the workers' start-up), else one is started and
     closed here."""

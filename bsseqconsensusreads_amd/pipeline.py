@@ -101,7 +101,7 @@ class FastqPiece:
     koff: tuple
 
     def ranges(self, a: int, b: int) -> list:
-        """kept families a..b-1 as submit_device pieces, one list per file."""
+        """kept families a..b-1 as bgzf.GpuBgzf.submit_device's pieces, one list per file."""
         return [[(self.text[d], int(self.koff[d][a]), int(self.koff[d][b]), self.event)] for d in range(2)]
 
 

@@ -21,7 +21,7 @@ from typing import Callable, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import bam, pipeline
+from . import bam, bgzf, pipeline
 from . import filter as _filter
 from . import records as R
 
@@ -33,7 +33,7 @@ EOF_BLOCK = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000
 class StreamJob:
     """What run() is to do, as plain values (a rank's job crosses a process boundary).
     molecular: None = step 5, else step 1 with this --min-consensus-base-quality.  gpu_bgzf: the
-    BAM's and the FASTQ pair's blocks are deflated on the engine's GPU (bam.GpuBgzf; the same
+    BAM's and the FASTQ pair's blocks are deflated on the engine's GPU (bgzf.GpuBgzf; the same
     records, other compressed bytes, files ≈4% larger).  filter (filter.FilterParams): every batch
     is filtered on the device after its vote (step5's `filter`); an Engine stream only.  defer:
     the span past which a template is deferred (step 5; default bam.DEFAULT_DEFER_SPAN, 0 = off;
@@ -45,10 +45,10 @@ class StreamJob:
     regions (the ranks' passes) = also cut before the first family of every new key contig pair (a
     piece keyed (pair, MINKEY)): a rank does not register cross keys (bsdc_io.cpp), so the deferred
     families of a contig's cross keys go between those pieces.
-    gpu_inflate: the input BAM's BGZF blocks are inflated on the engine's GPU (bam.GpuInflate; the
+    gpu_inflate: the input BAM's BGZF blocks are inflated on the engine's GPU (bgzf.GpuInflate; the
     same bytes, so the same output files); an Engine stream only.
     gpu_fastq: the FASTQ pair's text is formatted, checksummed and deflated on the engine's GPU
-    (Engine.fastq, bam.GpuBgzf.submit_device): the files of a gpu_bgzf run, byte for byte; needs
+    (Engine.fastq, bgzf.GpuBgzf.submit_device): the files of a gpu_bgzf run, byte for byte; needs
     `fastq`, an Engine stream only."""
 
     in_bam: str
@@ -277,12 +277,12 @@ class FrontEnd(_Stages):
 class BackEnd(_Stages):
     """builder -> writer: put(cons, chunk, cuts) hands a chunk's consensus over; a builder thread
     makes its output records (bam.duplex_records) while a writer thread encodes the chunk before
-    (bam.BamWriter / FastqWriter; gz_device: a call that gives the device whose GPU deflates,
-    bam.GpuBgzf).  cuts: (record index, key) -- everything before the index leaves as whole blocks
+    (bgzf.BamWriter / FastqWriter; gz_device: a call that gives the device whose GPU deflates,
+    bgzf.GpuBgzf).  cuts: (record index, key) -- everything before the index leaves as whole blocks
     and a piece with that key starts there, noted in `marks` ((BAM offset, FASTQ offsets x 2), sort
     key (key, tie)); the first mark is the header's, keyed first_key.  Once a chunk is written its
     pooled buffers go back to `bufs` and on_written(chunk) is called.  Leaving the `with` block
-    ends the threads; a failing writer closes its files quietly (bam.close_quietly).
+    ends the threads; a failing writer closes its files quietly (bgzf.close_quietly).
     fq_device (a call that gives the device): the FASTQ pair takes a chunk's text from HBM where
     its Consensus carries it (Consensus.fastq, pipeline.FastqPiece): the cuts become byte ranges of
     that text (FastqWriter.add_device), no records are built without a BAM, and the text is
@@ -338,13 +338,13 @@ class BackEnd(_Stages):
         w = fq = None
         th = self.threads
         try:
-            gz = (lambda: bam.GpuBgzf(self.gz_device())) if self.gz_device is not None else (lambda: None)
+            gz = (lambda: bgzf.GpuBgzf(self.gz_device())) if self.gz_device is not None else (lambda: None)
             if self.out_bam is not None:  # (a GpuBgzf each: one job in flight)
-                w = bam.BamWriter(self.out_bam, bam.output_header(self.header), self.level, gz(), self.fragment)
+                w = bgzf.BamWriter(self.out_bam, bam.output_header(self.header), self.level, gz(), self.fragment)
             if self.fastq is not None:
-                fq = bam.FastqWriter(self.fastq[0], self.fastq[1], self.level,
-                                     bam.GpuBgzf(self.fq_device()) if self.fq_device is not None else gz(),
-                                     self.fragment is not None)
+                fq = bgzf.FastqWriter(self.fastq[0], self.fastq[1], self.level,
+                                      bgzf.GpuBgzf(self.fq_device()) if self.fq_device is not None else gz(),
+                                      self.fragment is not None)
             self.marks.append(((0, 0, 0), self.first_key))  # (a first piece holds the header, if any)
             while True:
                 item = self.recq.get()
@@ -386,7 +386,7 @@ class BackEnd(_Stages):
                     self.fastq_counters = fq.gpu.counters()
         except BaseException as e:  # noqa: BLE001
             self.fault(e)
-            bam.close_quietly(w, fq)
+            bgzf.close_quietly(w, fq)
             while self.recq.get() is not None:  # drain so the builder never blocks
                 pass
 
@@ -406,7 +406,7 @@ def step5_stream(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, p
                  gpu_fastq: bool = False) -> dict:
     """step5 in bounded memory, pipelined (run); defer: the span past which a template is
     deferred (default DEFAULT_DEFER_SPAN; 0 = off); read_size: compressed bytes per refill;
-    filter: as step5's; gpu_inflate: the input's BGZF blocks inflate on the GPU (bam.GpuInflate);
+    filter: as step5's; gpu_inflate: the input's BGZF blocks inflate on the GPU (bgzf.GpuInflate);
     gpu_fastq: the FASTQ pair is formatted, checksummed and deflated on the GPU (StreamJob)."""
     job = StreamJob(in_bam, fasta, out_bam, fastq, prefix, threads, level, tags, gpu_bgzf, chunk_bytes, slack,
                     batch_bases, read_size, filter=filter, defer=defer, gpu_inflate=gpu_inflate, gpu_fastq=gpu_fastq)
@@ -546,7 +546,7 @@ def write_spill_bam(dst: str, header: "bam.BamHeader", spills: Sequence[str], le
     data = b"".join(open(x, "rb").read() for x in spills if x and os.path.exists(x))
     recs, n = bam.spill_sorted_records(data)
     del data
-    w = bam.BamWriter(dst, header, level)
+    w = bgzf.BamWriter(dst, header, level)
     try:
         w.add_raw(recs, threads)
     finally:
@@ -643,7 +643,7 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
         if ref is not None:
             (runner if runner is not None else eng).load_reference(ref)
         if job.gpu_inflate:  # (called on the decoder thread, on its own HIP stream)
-            inflater = bam.GpuInflate(eng.device)
+            inflater = bgzf.GpuInflate(eng.device)
         source = dict(path=job.in_bam, threads=job.threads, chunk_bytes=job.chunk_bytes, slack=job.slack,
                       read_size=job.read_size, runs=molecular, rng=job.rng, stats=rs, owner=job.owner, defer=dspan,
                       keys=late is not None, inflater=inflater)

@@ -207,3 +207,15 @@ def test_close_twice_and_after_a_failed_add(data, mode, tmp_path):
     h, r = bam.read_bam(str(tmp_path / "a.bam"))
     assert r.n == cuts[1]
     assert gzip.decompress(_read(str(tmp_path / "a1.fq.gz"))).count(b"\n") == 4 * (cuts[1] // 2)
+
+
+def test_moved_names_stay_importable_from_bam():
+    """the codecs and writers live in bgzf.py; bam.<name> is the same object, and the streaming
+    steps still resolve through the same module __getattr__"""
+    from bsseqconsensusreads_amd import bgzf, stream
+    for name in ("GpuBgzf", "GpuInflate", "_BgzfWriter", "BamWriter", "FastqWriter", "close_quietly"):
+        assert getattr(bam, name) is getattr(bgzf, name), name
+        assert name not in vars(bam), name
+    assert bam.step5_stream is stream.step5_stream and bam.molecular_stream is stream.molecular_stream
+    with pytest.raises(AttributeError):
+        bam.no_such_name
