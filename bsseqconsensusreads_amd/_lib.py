@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # BSDC_LIB_PATH: an alternative build of the same library (profiling A/B runs only)
 LIB_PATH = os.environ.get("BSDC_LIB_PATH") or os.path.join(HERE, "libbsdc.so")
 
-BSDC_ABI_VERSION = 18
+BSDC_ABI_VERSION = 19
 SMALL_BUCKETS = 8  # BSDC_SMALL_BUCKETS
 LARGE_BUCKETS = 6  # BSDC_LARGE_BUCKETS
 MODE_CONVERT, MODE_EXTEND, MODE_VOTE, MODE_DUMP = 1, 2, 4, 8
@@ -67,7 +67,7 @@ EXPORTS = ("bsdc_abi_version", "bsdc_ctx_create", "bsdc_ctx_set_params", "bsdc_c
            "bsdc_model_tables_fp64", "bsdc_agree_tables", "bsdc_phred_buckets", "bsdc_bgzf_scratch_bytes",
            "bsdc_bgzf_deflate", "bsdc_bgzf_pack", "bsdc_host_register", "bsdc_host_unregister", "bsdc_filter",
            "bsdc_bgzf_inflate", "bsdc_bgzf_inflate_host", "bsdc_fastq_text_bound", "bsdc_fastq_tmp_bytes",
-           "bsdc_fastq_format", "bsdc_bgzf_crc32")
+           "bsdc_fastq_format", "bsdc_bgzf_crc32", "bsdc_bam_bytes_bound", "bsdc_bam_tmp_bytes", "bsdc_bam_format")
 
 _lib = None
 
@@ -140,6 +140,13 @@ def load(path: str = LIB_PATH):
     lib.bsdc_fastq_format.restype = C.c_int32
     lib.bsdc_bgzf_crc32.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
     lib.bsdc_bgzf_crc32.restype = C.c_int32
+    lib.bsdc_bam_bytes_bound.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32]
+    lib.bsdc_bam_bytes_bound.restype = C.c_int64
+    lib.bsdc_bam_tmp_bytes.argtypes = [C.c_int64]
+    lib.bsdc_bam_tmp_bytes.restype = C.c_int64
+    lib.bsdc_bam_format.argtypes = [C.POINTER(ConsensusC), C.c_void_p, C.c_int32, C.c_int32, C.c_int64] + \
+        [C.c_void_p] * 8 + [C.c_int64, C.c_void_p, C.c_void_p]
+    lib.bsdc_bam_format.restype = C.c_int32
     if lib.bsdc_abi_version() != BSDC_ABI_VERSION:
         raise RuntimeError("libbsdc ABI %d != %d" % (lib.bsdc_abi_version(), BSDC_ABI_VERSION))
     if path == LIB_PATH:

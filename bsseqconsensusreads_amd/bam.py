@@ -903,6 +903,56 @@ def consensus_tags(cons, em: np.ndarray, molecular: bool = False, threads: int =
     return tab if pool is None else (tab, buf)
 
 
+def _mi_table(mi_names, mi_ids: np.ndarray):
+    """The MI names of the ids as (buf, off) of a packed table."""
+    mi_ids = np.asarray(mi_ids, np.int64)
+    if isinstance(mi_names, StringTable):  # decoded BAM: a packed table already
+        mt = _take_table(mi_names, mi_ids)
+    else:
+        uniq, inv = np.unique(mi_ids, return_inverse=True)
+        mt = _take_table(StringTable.from_list([(lambda m: m if isinstance(m, bytes) else m.encode())(
+            mi_names[int(i)]) for i in uniq]), inv)
+    return mt.buf, mt.off
+
+
+def family_aux(fam_rec_off, fam_src, fam_mi, raw: R.RawRecords, threads: int = 0,
+               fams: Optional[np.ndarray] = None) -> StringTable:
+    """The aux bytes both output records of a family carry -- RG:Z:A, MI:Z:<the family's MI>, and
+    RX:Z:<the consensus UMI of its records' RX tags> where they have one (libbsdc_io
+    bsdc_rx_consensus) -- as a packed table, one entry per family of `fams` (indices; default: every
+    family, emitted or not, as Engine.bam_records wants them before the launch).  Families:
+    fam_src[fam_rec_off[f]:fam_rec_off[f + 1]] are family f's input records, fam_mi[f] its MI id
+    (pipeline.Consensus' fields, or a FamilyBatch's fam_off / src / fam_mi)."""
+    lib = _load()
+    aux = _aux_table(raw)
+    fro = np.ascontiguousarray(fam_rec_off, np.int64)
+    fsrc = np.ascontiguousarray(fam_src, np.int64)
+    strand = np.ascontiguousarray(raw.mi_strand, np.int8)
+    nf_all = int(fro.shape[0]) - 1
+    em = np.arange(nf_all, dtype=np.int64) if fams is None else np.asarray(fams, np.int64)
+    F = int(em.shape[0])
+    # consensus UMI per family from its records' RX (libbsdc_io)
+    width = lib.bsdc_rx_consensus(nf_all, _ptr(fro), _ptr(fsrc), _ptr(strand), _ptr(aux.off),
+                                  _ptr(aux.buf if aux.buf.size else np.zeros(1, np.uint8)), None, None, int(threads))
+    rx = np.zeros(max(nf_all * max(width, 1), 1), np.uint8)
+    rx_len = np.zeros(max(nf_all, 1), np.int32)
+    if width > 0:
+        lib.bsdc_rx_consensus(nf_all, _ptr(fro), _ptr(fsrc), _ptr(strand), _ptr(aux.off), _ptr(aux.buf), _ptr(rx),
+                              _ptr(rx_len), int(threads))
+    mi = _mi_table(raw.mi_names, np.maximum(np.asarray(fam_mi, np.int64)[em], 0) if fams is None else
+                   np.asarray(fam_mi, np.int64)[em])
+    if width > 0:
+        rl = rx_len[em].astype(np.int64)
+        has = rl > 0
+        rxb = rx.reshape(-1, width)[em] if F else np.zeros((0, max(width, 1)), np.uint8)
+        rxv = (rxb[np.arange(width)[None, :] < rl[:, None]], np.concatenate([[0], np.cumsum(rl)]).astype(np.int64))
+        tag = (np.repeat(np.frombuffer(b"RXZ", np.uint8)[None, :], F, 0)[has].reshape(-1),
+               np.concatenate([[0], np.cumsum(np.where(has, 3, 0))]).astype(np.int64))
+        nul = (np.zeros(int(has.sum()), np.uint8), np.concatenate([[0], np.cumsum(has)]).astype(np.int64))
+        return _concat_fields([b"RGZA\0MIZ", mi, b"\0", tag, rxv, nul], F)
+    return _concat_fields([b"RGZA\0MIZ", mi, b"\0"], F)
+
+
 def duplex_records(cons, raw: R.RawRecords, prefix: str, threads: int = 0, molecular: bool = False,
                    pool: Optional["BufferPool"] = None) -> OutRecordsBam:
     """fgbio duplex output records for the emitted families of `cons`
@@ -916,40 +966,8 @@ def duplex_records(cons, raw: R.RawRecords, prefix: str, threads: int = 0, molec
     em = np.nonzero(_filter.kept(cons))[0]
     F = em.shape[0]
     n = 2 * F
-    # consensus UMI per family from its records' RX (libbsdc_io)
-    aux = _aux_table(raw)
-    fro = np.ascontiguousarray(cons.fam_rec_off, np.int64)
-    fsrc = np.ascontiguousarray(cons.fam_src, np.int64)
-    strand = np.ascontiguousarray(raw.mi_strand, np.int8)
-    nf_all = int(fro.shape[0]) - 1
-    width = lib.bsdc_rx_consensus(nf_all, _ptr(fro), _ptr(fsrc), _ptr(strand), _ptr(aux.off),
-                                  _ptr(aux.buf if aux.buf.size else np.zeros(1, np.uint8)), None, None, int(threads))
-    rx = np.zeros(max(nf_all * max(width, 1), 1), np.uint8)
-    rx_len = np.zeros(max(nf_all, 1), np.int32)
-    if width > 0:
-        lib.bsdc_rx_consensus(nf_all, _ptr(fro), _ptr(fsrc), _ptr(strand), _ptr(aux.off), _ptr(aux.buf), _ptr(rx),
-                              _ptr(rx_len), int(threads))
-    # names "prefix:MI" and aux RG/MI/RX, both mates of a family alike (packed tables, no per-family
-    # Python objects for the byte work)
-    mi_ids = cons.fam_mi[em].astype(np.int64)
-    if isinstance(raw.mi_names, StringTable):  # decoded BAM: a packed table already
-        mt = _take_table(raw.mi_names, mi_ids)
-    else:
-        uniq, inv = np.unique(mi_ids, return_inverse=True)
-        mt = _take_table(StringTable.from_list([(lambda m: m if isinstance(m, bytes) else m.encode())(
-            raw.mi_names[int(i)]) for i in uniq]), inv)
-    mi = (mt.buf, mt.off)
-    if width > 0:
-        rl = rx_len[em].astype(np.int64)
-        has = rl > 0
-        rxb = rx.reshape(-1, width)[em] if F else np.zeros((0, max(width, 1)), np.uint8)
-        rxv = (rxb[np.arange(width)[None, :] < rl[:, None]], np.concatenate([[0], np.cumsum(rl)]).astype(np.int64))
-        tag = (np.repeat(np.frombuffer(b"RXZ", np.uint8)[None, :], F, 0)[has].reshape(-1),
-               np.concatenate([[0], np.cumsum(np.where(has, 3, 0))]).astype(np.int64))
-        nul = (np.zeros(int(has.sum()), np.uint8), np.concatenate([[0], np.cumsum(has)]).astype(np.int64))
-        fam_aux = _concat_fields([b"RGZA\0MIZ", mi, b"\0", tag, rxv, nul], F)
-    else:
-        fam_aux = _concat_fields([b"RGZA\0MIZ", mi, b"\0"], F)
+    mi = _mi_table(raw.mi_names, cons.fam_mi[em])
+    fam_aux = family_aux(cons.fam_rec_off, cons.fam_src, cons.fam_mi, raw, threads, em)
     fam_names = _concat_fields([prefix.encode() + b":", mi], F)
     two = np.repeat(np.arange(F, dtype=np.int64), 2)
     names_t, auxs_t = _take_table(fam_names, two), _take_table(fam_aux, two)

@@ -331,6 +331,7 @@ class _BgzfWriter:
         self.gpu = gpu
         self.pending = None  # the BgzfJob submitted to the GPU, not yet written
         self.sinks = []
+        self.device_text = False  # add_device since the remainders were last brought back: they may hold bytes
         self.h = _P()
         if self._call("open", *open_args, C.byref(self.h)) != 0:
             raise self._err()
@@ -358,7 +359,41 @@ class _BgzfWriter:
             off += int(np.maximum(sz, 0).sum(dtype=np.int64))
             b += n
 
+    def add_device(self, pieces, threads: int = 0):
+        """Bytes that bsdc_fastq_format / bsdc_bam_format left in HBM join the files: pieces[d] =
+        file d's byte ranges (GpuBgzf.submit_device).  The protocol of add on the GPU path without
+        encode and take: the job before is written, this one submitted; its whole blocks come back
+        compressed with their CRC32s, the remainders stay on the device until a flush, the close or
+        a host add."""
+        if self.gpu is None:
+            raise ValueError("%s.add_device needs a GpuBgzf" % type(self).__name__)
+        self._drain(threads)
+        # host bytes added before (the BAM header at the open, add, add_raw) left their remainder in
+        # the sinks' tails: it goes in front of these bytes, as the device remainder (which add has
+        # emptied), so the bytes stay in order
+        for d, sink in enumerate(self.sinks):
+            # (a BAM header of many @SQ lines may hold whole blocks: they join the job too)
+            tail = np.empty(int(self.lib.bsdc_bgzf_sink_whole(sink)) + FRAMED_MAX, np.uint8)
+            n = int(self.lib.bsdc_bgzf_sink_take_tail(sink, _ptr(tail), tail.shape[0]))
+            if n < 0:
+                raise self._err()
+            if n:
+                self.gpu.push_remainder(d, tail[:n])
+        self.device_text = True
+        self.pending = self.gpu.submit_device(pieces)
+
+    def _remainders(self, threads: int):
+        """the device remainders (< BLOCK_BYTES each) brought to the sinks' tails"""
+        if not self.device_text:
+            return
+        self._drain(threads)
+        for sink, r in zip(self.sinks, self.gpu.take_remainders()):
+            if r.shape[0] and self.lib.bsdc_bgzf_sink_append(sink, _ptr(r), int(r.shape[0])) != 0:
+                raise self._err()
+        self.device_text = False
+
     def add(self, recs: bam.OutRecordsBam, threads: int = 0):
+        self._remainders(threads)  # (host bytes after device bytes: in order)
         keep = []
         r = bam._records_struct(recs, keep)
         if self._call("add" if self.gpu is None else "encode", self.h, C.byref(r), int(threads)) != 0:
@@ -381,6 +416,7 @@ class _BgzfWriter:
             self.pending = BgzfJob(nb, crc, raw.data_ptr())
 
     def _flush(self, threads: int) -> tuple:
+        self._remainders(threads)
         self._drain(threads)
         if self._call("flush", self.h, int(threads)) != 0:
             raise self._err()
@@ -389,6 +425,7 @@ class _BgzfWriter:
     def close(self, threads: int = 0):
         if self.h:
             try:
+                self._remainders(threads)
                 self._drain(threads)
             finally:
                 h, self.h = self.h, _P()
@@ -400,7 +437,8 @@ class _BgzfWriter:
 class BamWriter(_BgzfWriter):
     """Streaming BAM writer (bsdc_bam_writer): header at open, records added in order, the same
     bytes as bam.write_bam of all the records at once -- or, with `gpu`, every whole block deflated
-    on the GPU."""
+    on the GPU; add_device then takes records that bsdc_bam_format wrote in HBM (one file: pieces =
+    [its byte ranges]), the file a writer fed the same records by add on the GPU path writes."""
 
     def __init__(self, path: str, header: bam.BamHeader, level: int = 6, gpu: Optional["GpuBgzf"] = None,
                  fragment: Optional[str] = None):
@@ -420,6 +458,7 @@ class BamWriter(_BgzfWriter):
     def add_raw(self, data: bytes, threads: int = 0):
         """Raw BAM records (block_size-prefixed), as a stream chunk holds them (host deflate)."""
         if data:
+            self._remainders(threads)  # (host bytes after device records: in order)
             buf = np.frombuffer(data, np.uint8)
             if self.lib.bsdc_bam_writer_raw(self.h, _ptr(buf), buf.shape[0], int(threads)) != 0:
                 raise self._err()
@@ -447,52 +486,9 @@ class FastqWriter(_BgzfWriter):
                  fragment: bool = False):
         super().__init__("fastq", path1, gpu, path1.encode(), path2.encode(), int(level))
         self.sinks = [self.lib.bsdc_fastq_writer_sink(self.h, d) for d in range(2)]
-        self.device_text = False  # add_device since the remainders were last brought back: they may hold bytes
         if fragment and self.lib.bsdc_fastq_writer_fragment(self.h) != 0:  # (no EOF blocks: ranks.assemble)
             raise self._err()
 
-    def add_device(self, pieces, threads: int = 0):
-        """Text that bsdc_fastq_format left in HBM joins the pair: pieces[d] = file d's byte ranges
-        (GpuBgzf.submit_device).  The protocol of add on the GPU path without encode and take: the
-        job before is written, this one submitted; its whole blocks come back compressed with their
-        CRC32s, the remainders stay on the device until a flush, the close or a host add."""
-        if self.gpu is None:
-            raise ValueError("FastqWriter.add_device needs a GpuBgzf")
-        self._drain(threads)
-        # host text added before (add) left its remainder in the sinks' tails: it goes in front of
-        # this text, as the device remainder (which add has emptied), so the bytes stay in order
-        for d, sink in enumerate(self.sinks):
-            tail = np.empty(FRAMED_MAX, np.uint8)
-            n = int(self.lib.bsdc_bgzf_sink_take_tail(sink, _ptr(tail), tail.shape[0]))
-            if n < 0:
-                raise self._err()
-            if n:
-                self.gpu.push_remainder(d, tail[:n])
-        self.device_text = True
-        self.pending = self.gpu.submit_device(pieces)
-
-    def _remainders(self, threads: int):
-        """the device remainders (< BLOCK_BYTES each) brought to the sinks' tails"""
-        if not self.device_text:
-            return
-        self._drain(threads)
-        for sink, r in zip(self.sinks, self.gpu.take_remainders()):
-            if r.shape[0] and self.lib.bsdc_bgzf_sink_append(sink, _ptr(r), int(r.shape[0])) != 0:
-                raise self._err()
-        self.device_text = False
-
-    def add(self, recs: bam.OutRecordsBam, threads: int = 0):
-        self._remainders(threads)  # (host text after device text: in order)
-        super().add(recs, threads)
-
     def flush(self, threads: int = 0) -> Tuple[int, int]:
         """Everything added so far written as whole BGZF blocks; -> (length of file 1, of file 2)."""
-        self._remainders(threads)
         return self._flush(threads)
-
-    def close(self, threads: int = 0):
-        try:
-            if self.h:
-                self._remainders(threads)
-        finally:
-            super().close(threads)

@@ -60,6 +60,10 @@ def parse(argv):
         p.add_argument("--gpu-fastq", default="false", choices=("true", "false"),
                        help="format, checksum and deflate the FASTQ pair on the GPU (streaming, --gpus 1; needs "
                             "--fastq1/--fastq2; the files of a --gpu-bgzf run)")
+        p.add_argument("--gpu-bam", default="false", choices=("true", "false"),
+                       help="write, checksum and deflate the output BAM's records (consensus tags included) on the "
+                            "GPU (streaming, --gpus 1; needs OUT.bam; implies the GPU deflate for the BAM; the file "
+                            "of a --gpu-bgzf run)")
         p.add_argument("--batch-bases", type=int, default=None, help="device batch budget in bases")
         p.add_argument("--chunk-mb", type=int, default=64, help="--stream: record MiB per chunk")
         if name == "step5":
@@ -118,6 +122,13 @@ def parse(argv):
             ap.error("--gpu-fastq is not supported with --gpus %d yet (one process, one GPU)" % a.gpus)
         if a.stream == "false":
             ap.error("--gpu-fastq applies to the streaming step only: not with --stream false")
+    if a.gpu_bam == "true":
+        if a.output == "-":
+            ap.error("--gpu-bam needs the output BAM: not with OUT.bam '-'")
+        if getattr(a, "gpus", 1) > 1:
+            ap.error("--gpu-bam is not supported with --gpus %d yet (one process, one GPU)" % a.gpus)
+        if a.stream == "false":
+            ap.error("--gpu-bam applies to the streaming step only: not with --stream false")
     if a.gpu_inflate == "true" and a.stream == "false":
         print("warning: --gpu-inflate applies to the streaming step only; --stream false inflates on the host",
               file=sys.stderr)
@@ -218,7 +229,11 @@ def main(argv=None) -> int:
                 info = bam.step5_stream(a.input, a.reference, out, eng, a.read_name_prefix, a.threads, a.compression,
                                         fq, tags=a.output_per_base_tags == "true", chunk_bytes=a.chunk_mb << 20,
                                         batch_bases=a.batch_bases, gpu_bgzf=a.gpu_bgzf == "true", filter=flt,
-                                        gpu_inflate=a.gpu_inflate == "true", gpu_fastq=a.gpu_fastq == "true")
+                                        gpu_inflate=a.gpu_inflate == "true", gpu_fastq=a.gpu_fastq == "true",
+                                        gpu_bam=a.gpu_bam == "true")
+            elif a.cmd == "step5" and a.gpu_bam == "true":
+                raise ValueError("--gpu-bam applies to the streaming step only: %s is not coordinate-sorted "
+                                 "and would be read whole" % a.input)
             elif a.cmd == "step5" and a.gpu_fastq == "true":
                 raise ValueError("--gpu-fastq applies to the streaming step only: %s is not coordinate-sorted "
                                  "and would be read whole" % a.input)
@@ -231,7 +246,8 @@ def main(argv=None) -> int:
                                             tags=a.output_per_base_tags == "true", chunk_bytes=a.chunk_mb << 20,
                                             batch_bases=a.batch_bases, gpu_bgzf=a.gpu_bgzf == "true",
                                             min_consensus_base_quality=a.min_consensus_base_quality, filter=flt,
-                                            gpu_inflate=a.gpu_inflate == "true", gpu_fastq=a.gpu_fastq == "true")
+                                            gpu_inflate=a.gpu_inflate == "true", gpu_fastq=a.gpu_fastq == "true",
+                                            gpu_bam=a.gpu_bam == "true")
             else:
                 info = bam.molecular(a.input, out, eng, a.read_name_prefix, a.threads, a.compression, fq,
                                      tags=a.output_per_base_tags == "true",

@@ -5,10 +5,8 @@
 // forward records (picard SamToFastq's, main.snake.py:58-67,167-177).
 //
 // bsdc_fastq_format, three launches and the text on one stream, no host step between them:
-//  1. k_fq_sum: a workgroup sums the byte counts of its 1024 families, per file;
-//  2. k_fq_scan: one workgroup scans the workgroups' sums in place (tiles of 256 with a carry) and
-//     writes the totals to off[d][n_fam];
-//  3. k_fq_off: each workgroup scans its families' counts again from its base -> off[d][f];
+//  1-3. the offset scan of bsdc_devtext.h (k_scan_sum / k_scan_scan / k_scan_off, shared with
+//     bsdc_bam.hip) over the families' byte counts per file -> off[d][f], off[d][n_fam] = the total;
 //  4. k_fq_text: one wavefront per (family, end).  A record starts at any byte of the text, so a
 //     lane owns one ALIGNED dword of the destination at a time: it assembles the dword's four
 //     bytes in a register and stores it whole; only a record's first and last partial dword (and
@@ -27,16 +25,14 @@
 #include <stdint.h>
 
 #include "../../include/bsdc.h"
+#include "bsdc_devtext.h"
 
 namespace {
 
-#define BSDC_HD __host__ __device__ __forceinline__
+using namespace bsdc_devtext;  // kT, kFamPerGroup, nt16x4, the scan
 
-constexpr int kT = 256;    // threads per workgroup
 constexpr int kSeg = 255;  // bytes per thread segment of a BGZF block (bsdc_bgzf.hip's segmentation)
 constexpr int kBlock = kT * kSeg;
-constexpr int kFamPerThread = 4;
-constexpr int kFamPerGroup = kT * kFamPerThread;
 constexpr int kMaxName = 254;
 constexpr uint32_t kPoly = 0xEDB88320u;  // the gzip polynomial, reflected: bit 31 is x^0
 
@@ -147,23 +143,6 @@ BSDC_HD int64_t fq_bytes(const FqArgs &A, int64_t f, int d) {
     return fq_kept(A, f) ? 8 + fq_name_len(A, f) + 2 * fq_len(A, f, d) : 0;
 }
 
-// four nt16 codes (one per byte) -> their letters of "=ACMGRSVTWYHKDBN"
-BSDC_HD uint32_t nt16x4(uint32_t c) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    // v_perm_b32: selector bytes 0..3 pick from the second operand, 4..7 from the first
-    const uint32_t sel = c & 0x07070707u;
-    const uint32_t lo = __builtin_amdgcn_perm(0x56535247u /* GRSV */, 0x4D43413Du /* =ACM */, sel);
-    const uint32_t hi = __builtin_amdgcn_perm(0x4E42444Bu /* KDBN */, 0x48595754u /* TWYH */, sel);
-    const uint32_t m = ((c >> 3) & 0x01010101u) * 0xffu;
-    return (lo & ~m) | (hi & m);
-#else
-    const char *t = "=ACMGRSVTWYHKDBN";
-    uint32_t v = 0;
-    for (int b = 0; b < 4; b++) v |= (uint32_t)(uint8_t)t[(c >> (8 * b)) & 15u] << (8 * b);
-    return v;
-#endif
-}
-
 // One record (family f, end d): name nm[0, nl), packed bases sq, qualities ql, L bases.
 struct FqRec {
     const uint8_t *nm, *sq, *ql;
@@ -242,70 +221,8 @@ BSDC_HD FqRec fq_rec(const FqArgs &A, int64_t f, int d) {
     return r;
 }
 
-// exclusive scan of one value per thread over the workgroup (sh: 2 * kT values); *total = the sum
-__device__ int64_t group_scan(int64_t v, int64_t *sh, int64_t *total) {
-    const int t = threadIdx.x;
-    int cur = 0;
-    sh[t] = v;
-    __syncthreads();
-    for (int o = 1; o < kT; o <<= 1) {
-        int64_t x = sh[cur * kT + t];
-        if (t >= o) x += sh[cur * kT + t - o];
-        cur ^= 1;
-        sh[cur * kT + t] = x;
-        __syncthreads();
-    }
-    const int64_t inc = sh[cur * kT + t];
-    *total = sh[cur * kT + kT - 1];
-    __syncthreads();
-    return inc - v;
-}
-
-__global__ __launch_bounds__(kT) void k_fq_sum(FqArgs A) {
-    __shared__ int64_t sh[2 * kT];
-    const int64_t f0 = (int64_t)blockIdx.x * kFamPerGroup + threadIdx.x * kFamPerThread;
-    for (int d = 0; d < 2; d++) {
-        int64_t s = 0, total;
-        for (int j = 0; j < kFamPerThread; j++)
-            if (f0 + j < A.n_fam) s += fq_bytes(A, f0 + j, d);
-        group_scan(s, sh, &total);
-        if (threadIdx.x == 0) A.bsum[d * (A.groups + 1) + blockIdx.x] = total;
-    }
-}
-
-__global__ __launch_bounds__(kT) void k_fq_scan(FqArgs A) {
-    __shared__ int64_t sh[2 * kT];
-    for (int d = 0; d < 2; d++) {
-        int64_t *b = A.bsum + d * (A.groups + 1);
-        int64_t carry = 0;
-        for (int64_t g0 = 0; g0 < A.groups; g0 += kT) {
-            const int64_t g = g0 + threadIdx.x;
-            const int64_t v = g < A.groups ? b[g] : 0;
-            int64_t total;
-            const int64_t ex = group_scan(v, sh, &total);
-            if (g < A.groups) b[g] = carry + ex;
-            carry += total;
-        }
-        if (threadIdx.x == 0) A.off[d][A.n_fam] = carry;
-    }
-}
-
-__global__ __launch_bounds__(kT) void k_fq_off(FqArgs A) {
-    __shared__ int64_t sh[2 * kT];
-    const int64_t f0 = (int64_t)blockIdx.x * kFamPerGroup + threadIdx.x * kFamPerThread;
-    for (int d = 0; d < 2; d++) {
-        int64_t n[kFamPerThread], s = 0, total;
-        for (int j = 0; j < kFamPerThread; j++) {
-            n[j] = f0 + j < A.n_fam ? fq_bytes(A, f0 + j, d) : 0;
-            s += n[j];
-        }
-        int64_t o = A.bsum[d * (A.groups + 1) + blockIdx.x] + group_scan(s, sh, &total);
-        for (int j = 0; j < kFamPerThread; j++) {
-            if (f0 + j < A.n_fam) A.off[d][f0 + j] = o;
-            o += n[j];
-        }
-    }
-}
+BSDC_HD int64_t scan_bytes(const FqArgs &A, int64_t f, int d) { return fq_bytes(A, f, d); }
+BSDC_HD int64_t *scan_off(const FqArgs &A, int d) { return A.off[d]; }
 
 __global__ __launch_bounds__(kT) void k_fq_text(FqArgs A) {
     const int64_t w = (int64_t)blockIdx.x * (kT / 64) + (threadIdx.x >> 6);
@@ -367,10 +284,8 @@ int32_t bsdc_fastq_format(const bsdc_consensus *out, const uint8_t *filt, int64_
     A.bsum = reinterpret_cast<int64_t *>(tmp);
     A.groups = (n_fam + kFamPerGroup - 1) / kFamPerGroup;
     hipStream_t st = (hipStream_t)stream;
-    if (A.groups) hipLaunchKernelGGL(k_fq_sum, dim3((unsigned)A.groups), dim3(kT), 0, st, A);
-    hipLaunchKernelGGL(k_fq_scan, dim3(1), dim3(kT), 0, st, A);
+    launch_scan<2>(A, st);
     if (A.groups) {
-        hipLaunchKernelGGL(k_fq_off, dim3((unsigned)A.groups), dim3(kT), 0, st, A);
         const int64_t waves = 2 * n_fam;
         hipLaunchKernelGGL(k_fq_text, dim3((unsigned)((waves + kT / 64 - 1) / (kT / 64))), dim3(kT), 0, st, A);
     }

@@ -68,6 +68,19 @@ class FastqText:
     total: Optional[tuple] = None  # (file 1's bytes, file 2's), once fetched
 
 
+@dataclass
+class BamText:
+    """What Engine.bam_records leaves on a DeviceBatch: the BAM records of its kept families in HBM
+    (bsdc_bam_format).  rec: the bytes (uint8, `cap` of them allocated); off: int64 [F + 1] on the
+    device, the families' byte offsets, off[F] = the records' size; event: recorded after the
+    launch.  Dropping the object releases the records."""
+
+    rec: torch.Tensor
+    off: torch.Tensor
+    cap: int
+    event: "torch.cuda.Event"
+
+
 class DeviceBatch:
     """A FamilyBatch resident in HBM plus its output buffers."""
 
@@ -116,6 +129,7 @@ class DeviceBatch:
                 self.ss_wdepth = torch.zeros(nw, dtype=torch.int16, device=device)
                 self.ss_werr = torch.zeros(nw, dtype=torch.int16, device=device)
         self.fastq: Optional[FastqText] = None  # Engine.fastq
+        self.bamrec: Optional[BamText] = None  # Engine.bam_records
         self.filt = self.masked = None
         if filt:  # bsdc_filter's outputs: reason bits per family, newly masked columns per end
             self.filt = torch.zeros(max(F, 1), dtype=torch.uint8, device=device)
@@ -170,10 +184,13 @@ class DeviceBatch:
     def fetch(self, alloc=None, ss: bool = True, seqqual: bool = True):
         """-> dict of numpy arrays (consensus and, if dumped, the post-tool records; after
         Engine.filter also "filt" [F] and "masked" [F, 2]).  ss=False leaves the single-strand rows
-        of a tags batch in HBM (a filtered output without consensus tags).  seqqual=False (after
-        Engine.fastq, when no BAM is written): "status", "len", ("filt", "masked") and "fastq_total"
-        (the two texts' sizes, checked against the buffers) only -- the bases and qualities stay
-        in HBM, where the text was made of them; `ss` does not apply and `alloc` is refused.  The copies
+        of a tags batch in HBM (a filtered output without consensus tags, or one whose records
+        Engine.bam_records wrote there).  seqqual=False (after Engine.fastq or Engine.bam_records,
+        when no output is formatted on the host): "status", "len", ("filt", "masked"), "fastq_total"
+        (the two texts' sizes, checked against the buffers) and "bam_off" only -- the bases and
+        qualities stay in HBM, where the outputs were made of them; `ss` does not apply and `alloc`
+        is refused.  After Engine.bam_records every form brings "bam_off" (int64 [F + 1], 8 bytes a
+        family: where each family's records start, the last one their size).  The copies
         are queued together on the current stream into pinned host memory (torch's caching host
         allocator), then one synchronize.  With alloc(nbytes) -> uint8 array (a fleet worker's
         shared segment) the outputs land in that buffer instead, so they leave the worker by name."""
@@ -188,6 +205,8 @@ class DeviceBatch:
         ss = ss and self.tags
         if self.filt is not None:
             t.update(filt=self.filt[:F], masked=self.masked[:2 * F])
+        if self.bamrec is not None:
+            t.update(bam_off=self.bamrec.off)
         if ss:
             t.update(ss_len=self.ss_len[:4 * F], ss_base=self.ss_base[:n], ss_qual=self.ss_qual[:n],
                      ss_depth=self.ss_depth[:n], ss_err=self.ss_err[:n])
@@ -222,6 +241,8 @@ class DeviceBatch:
         if self.filt is not None:
             out["filt"] = a["filt"]
             out["masked"] = a["masked"].view(np.uint16).astype(np.int32).reshape(F, 2)
+        if self.bamrec is not None:
+            out["bam_off"] = a["bam_off"].view(np.int64)
         if ss:
             out["ss_len"] = a["ss_len"].view(np.uint16).astype(np.int32).reshape(F, 4)
             out["ss_base"] = a["ss_base"].reshape(F, 4, self.stride)
@@ -244,9 +265,13 @@ class DeviceBatch:
 
     def _fetch_small(self):
         F = self.n_fam
-        if self.fastq is None:
-            raise ValueError("fetch(seqqual=False) needs Engine.fastq on the batch first")
-        t = {"status": self.status[:F], "len": self.len[:2 * F], "fastq_total": self.fastq.off[:, F].contiguous()}
+        if self.fastq is None and self.bamrec is None:
+            raise ValueError("fetch(seqqual=False) needs Engine.fastq or Engine.bam_records on the batch first")
+        t = {"status": self.status[:F], "len": self.len[:2 * F]}
+        if self.fastq is not None:
+            t.update(fastq_total=self.fastq.off[:, F].contiguous())
+        if self.bamrec is not None:
+            t.update(bam_off=self.bamrec.off)
         if self.filt is not None:
             t.update(filt=self.filt[:F], masked=self.masked[:2 * F])
         h = {k: v.to("cpu", non_blocking=True) for k, v in t.items()}
@@ -256,9 +281,12 @@ class DeviceBatch:
         if self.filt is not None:
             out["filt"] = h["filt"].numpy()
             out["masked"] = h["masked"].numpy().view(np.uint16).astype(np.int32).reshape(F, 2)
-        self.fastq.total = out["fastq_total"] = tuple(int(x) for x in h["fastq_total"].numpy())
-        for d in range(2):
-            assert 0 <= self.fastq.total[d] <= self.fastq.cap[d], (self.fastq.total, self.fastq.cap)
+        if self.bamrec is not None:
+            out["bam_off"] = h["bam_off"].numpy()
+        if self.fastq is not None:
+            self.fastq.total = out["fastq_total"] = tuple(int(x) for x in h["fastq_total"].numpy())
+            for d in range(2):
+                assert 0 <= self.fastq.total[d] <= self.fastq.cap[d], (self.fastq.total, self.fastq.cap)
         return out
 
 
@@ -433,6 +461,48 @@ class Engine:
             ev.record(s)
         db.fastq = FastqText(text, off, (cap, cap), ev, off_h)
         return db.fastq
+
+    def bam_records(self, db: DeviceBatch, names, aux, molecular: bool = False, tags: bool = True,
+                    stream: Optional[torch.cuda.Stream] = None) -> BamText:
+        """The output BAM's records of the batch's kept families written where the consensus lies
+        (bsdc_bam_format), enqueued on the stream that ran the vote, after it and after `filter`.
+        names, aux: the families' read names and aux bytes (RG / MI / RX), one each, as packed tables
+        (.buf, .off: bam.family_names, bam.family_aux).  tags: fgbio's consensus tags follow, from
+        the single-strand rows (the batch was uploaded with tags=True).  The tables go up, a buffer of
+        the size known beforehand (bsdc_bam_bytes_bound) is allocated, and db.bamrec holds it with an
+        event recorded behind the launch."""
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        F = db.n_fam
+        if tags and not db.tags:
+            raise ValueError("bam_records(tags=True): the batch was uploaded without tags=True")
+        host = []
+        for t in (names, aux):
+            off_h = np.ascontiguousarray(t.off, np.int64)
+            if off_h.shape[0] != F + 1:
+                raise ValueError("one entry per family: %d offsets for %d families" % (off_h.shape[0], F))
+            off_h = off_h - off_h[0]
+            nb = int(off_h[-1])
+            buf_h = np.ascontiguousarray(t.buf[int(t.off[0]):int(t.off[0]) + nb], np.uint8)
+            host.append((off_h, buf_h if nb else np.zeros(1, np.uint8), nb))
+        cap = int(self.lib.bsdc_bam_bytes_bound(F, host[0][2], host[1][2], db.stride, 1 if molecular else 0,
+                                                1 if tags else 0))
+        with torch.cuda.device(self.device), torch.cuda.stream(s):
+            dev = [(torch.from_numpy(o).to(self.device), torch.from_numpy(b).to(self.device)) for o, b, _ in host]
+            rec = torch.empty(max(cap, 16), dtype=torch.uint8, device=self.device)
+            off = torch.empty(F + 1, dtype=torch.int64, device=self.device)
+            tmp = torch.empty(int(self.lib.bsdc_bam_tmp_bytes(F)), dtype=torch.uint8, device=self.device)
+            p = lambda t: C.c_void_p(_dptr(t))  # noqa: E731
+            rc = self.lib.bsdc_bam_format(C.byref(db._o), p(db.filt) if db.filt is not None else None,
+                                          1 if molecular else 0, 1 if tags else 0, F,
+                                          p(dev[0][0]), p(dev[0][1]), C.c_void_p(host[0][0].ctypes.data),
+                                          p(dev[1][0]), p(dev[1][1]), C.c_void_p(host[1][0].ctypes.data),
+                                          p(off), p(rec), cap, p(tmp), C.c_void_p(s.cuda_stream))
+            if rc != 0:
+                raise RuntimeError("bsdc_bam_format failed (%d)" % rc)
+            ev = torch.cuda.Event()
+            ev.record(s)
+        db.bamrec = BamText(rec, off, cap, ev)
+        return db.bamrec
 
     def tables(self):
         lr = np.zeros(256, np.int64)

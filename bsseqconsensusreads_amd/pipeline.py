@@ -85,6 +85,27 @@ class Consensus:
     # with run_batches(fastq_names=...): one FastqPiece per batch, the kept families' FASTQ text in
     # HBM (Engine.fastq); seq / qual are then empty ([F, 2, 0]) when they were left on the device
     fastq: Optional[list] = None
+    # with run_batches(bam_tables=...): one BamPiece per batch, the kept families' BAM records in
+    # HBM (Engine.bam_records); the ss rows then stayed on the device (ss is None)
+    bamrec: Optional[list] = None
+
+
+@dataclass
+class BamPiece:
+    """One batch's BAM records on the device and where its kept families lie in them: rec = the
+    uint8 device tensor, event = recorded behind the launch, kept = the batch's kept families, koff
+    int64 [kept + 1] = the byte offset of each kept family's records (R1 then R2; the device's own
+    offsets, fetched), the last one = the records' size, checked against the buffer.  Dropping it
+    releases the records."""
+
+    rec: object
+    event: object
+    kept: int
+    koff: np.ndarray
+
+    def ranges(self, a: int, b: int) -> list:
+        """kept families a..b-1 as bgzf.GpuBgzf.submit_device's pieces of the one file."""
+        return [(self.rec, int(self.koff[a]), int(self.koff[b]), self.event)]
 
 
 @dataclass
@@ -304,7 +325,8 @@ def materialize_ranges(plan: FamilyPlan, ranges, images=None) -> List[FamilyBatc
 
 def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
                 timing: Optional[dict] = None, filter: Optional[FilterParams] = None,
-                molecular: bool = False, fastq_names=None, seqqual: bool = True) -> List[Consensus]:
+                molecular: bool = False, fastq_names=None, seqqual: bool = True, bam_tables=None,
+                bam_tags: bool = True) -> List[Consensus]:
     """Materialized batches (any iterable, taken one at a time) through the kernels, one launch
     each, output per batch in order; a batch uploads and launches before the one before it is
     fetched.  `timing`: seconds added per host step (upload, fetch = wait + copy out, unpack).
@@ -312,7 +334,11 @@ def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
     step-1 records), which needs the tags' rows there; they are copied out only with `tags`.
     `fastq_names` (batch -> its families' read names, a packed table): each batch's FASTQ text is
     formatted on the device right after its vote or filter (Engine.fastq) and its Consensus carries
-    the handle (Consensus.fastq); seqqual=False then leaves the bases and qualities in HBM."""
+    the handle (Consensus.fastq); seqqual=False then leaves the bases and qualities in HBM.
+    `bam_tables` (batch -> its families' read names and aux bytes, two packed tables): each batch's
+    BAM records are written on the device after its vote or filter (Engine.bam_records; bam_tags:
+    with the consensus tags, whose rows the vote then leaves there) and its Consensus carries the
+    handle (Consensus.bamrec); the ss rows are not fetched."""
     import time
     T = timing if timing is not None else {}
     parts: List[Consensus] = []
@@ -320,21 +346,28 @@ def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
 
     def out(fb, db):
         t0 = time.perf_counter()
-        o = db.fetch(ss=tags) if seqqual or db.fastq is None else db.fetch(seqqual=False)
+        if seqqual or (db.fastq is None and db.bamrec is None):
+            o = db.fetch(ss=tags and db.bamrec is None)
+        else:
+            o = db.fetch(seqqual=False)
         t1 = time.perf_counter()
         parts.append(consensus_from_output(fb, o))
         if db.fastq is not None:
             parts[-1].fastq = [_fastq_piece(db, parts[-1])]
+        if db.bamrec is not None:
+            parts[-1].bamrec = [_bam_piece(db, parts[-1], o["bam_off"])]
         T["fetch"] = T.get("fetch", 0.0) + t1 - t0
         T["unpack"] = T.get("unpack", 0.0) + time.perf_counter() - t1
     for fb in batches:
         t0 = time.perf_counter()
-        db = engine.upload(fb, tags=tags, filt=filter is not None)
+        db = engine.upload(fb, tags=tags or (bam_tables is not None and bam_tags), filt=filter is not None)
         engine.run(db, mode | (MODE_TAGS if db.tags else 0))
         if filter is not None:
             engine.filter(db, filter, molecular)
         if fastq_names is not None:
             engine.fastq(db, fastq_names(fb))
+        if bam_tables is not None:
+            engine.bam_records(db, *bam_tables(fb), molecular=molecular, tags=bam_tags)
         T["upload"] = T.get("upload", 0.0) + time.perf_counter() - t0
         if prev is not None:
             out(*prev)
@@ -361,12 +394,26 @@ def _fastq_piece(db, cons: Consensus) -> FastqPiece:
     return FastqPiece(fq.text, fq.event, int(k.shape[0]), koff)
 
 
+def _bam_piece(db, cons: Consensus, off: np.ndarray) -> BamPiece:
+    """The batch's device records as a BamPiece: the fetched offsets at the kept families, the
+    device's total checked against the buffer (a stream synchronised by the fetch before)."""
+    from .filter import kept
+    off = np.asarray(off, np.int64)
+    total = int(off[-1])
+    k = np.nonzero(kept(cons))[0]
+    if not 0 <= total <= db.bamrec.cap or (np.diff(off) != 0).sum() != k.shape[0]:
+        raise RuntimeError("BAM records: the device wrote %d bytes for %d families (buffer %d, %d kept)" % (
+            total, int((np.diff(off) != 0).sum()), db.bamrec.cap, int(k.shape[0])))
+    return BamPiece(db.bamrec.rec, db.bamrec.event, int(k.shape[0]), np.concatenate([off[k], off[-1:]]))
+
+
 def concat_consensus(parts: List[Consensus]) -> Consensus:
     """Consensus of consecutive family ranges -> one Consensus in range order (strides padded to
     the widest)."""
     if len(parts) == 1:
         return parts[0]
     fastq = [x for p in parts for x in p.fastq] if parts and all(p.fastq is not None for p in parts) else None
+    bamrec = [x for p in parts for x in p.bamrec] if parts and all(p.bamrec is not None for p in parts) else None
     if not parts:
         z = np.zeros(0, np.int32)
         return Consensus(z, np.zeros(0, np.uint8), np.zeros((0, 2), np.int32), np.zeros((0, 2, 16), np.uint8),
@@ -401,7 +448,7 @@ def concat_consensus(parts: List[Consensus]) -> Consensus:
     return Consensus(np.concatenate([p.fam_mi for p in parts]), np.concatenate([p.status for p in parts]),
                      np.concatenate([p.length for p in parts]), np.concatenate([pad(p.seq) for p in parts]),
                      np.concatenate([pad(p.qual) for p in parts]), fro.astype(np.int64),
-                     np.concatenate([np.asarray(p.fam_src, np.int64) for p in parts]), ss, filt, masked, fastq)
+                     np.concatenate([np.asarray(p.fam_src, np.int64) for p in parts]), ss, filt, masked, fastq, bamrec)
 
 
 def _tools_batched(engine: Engine, raw: R.RawRecords, batch_bases: Optional[int]) -> OutRecords:

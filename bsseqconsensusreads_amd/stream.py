@@ -49,7 +49,10 @@ class StreamJob:
     same bytes, so the same output files); an Engine stream only.
     gpu_fastq: the FASTQ pair's text is formatted, checksummed and deflated on the engine's GPU
     (Engine.fastq, bgzf.GpuBgzf.submit_device): the files of a gpu_bgzf run, byte for byte; needs
-    `fastq`, an Engine stream only."""
+    `fastq`, an Engine stream only.
+    gpu_bam: the output BAM's records are written in HBM from the consensus (Engine.bam_records),
+    checksummed and deflated there (bgzf.BamWriter.add_device): the file of a gpu_bgzf run, byte
+    for byte; needs `out_bam`, an Engine stream only; implies the GPU deflate for the BAM."""
 
     in_bam: str
     fasta: Optional[str]
@@ -75,6 +78,7 @@ class StreamJob:
     first_key: Optional[tuple] = None
     regions: bool = False
     gpu_fastq: bool = False
+    gpu_bam: bool = False
     gpu_inflate: bool = False  # (stays the last field)
 
 
@@ -287,17 +291,22 @@ class BackEnd(_Stages):
     its Consensus carries it (Consensus.fastq, pipeline.FastqPiece): the cuts become byte ranges of
     that text (FastqWriter.add_device), no records are built without a BAM, and the text is
     released once the chunk is written.  A chunk without device text (a split_ext plan) goes the
-    host way through the same writer.  fastq_counters: the pair's GpuBgzf counters at the close."""
+    host way through the same writer.  fastq_counters: the pair's GpuBgzf counters at the close.
+    bam_device (a call that gives the device): likewise the BAM takes a chunk's records from HBM
+    where its Consensus carries them (Consensus.bamrec, pipeline.BamPiece; BamWriter.add_device):
+    no tagged records are built for such a chunk (untagged ones only when the FASTQ pair is
+    formatted on the host); bam_counters: the BAM's GpuBgzf counters at the close."""
 
     def __init__(self, fault: Fault, out_bam: Optional[str], fastq, header, prefix: str, threads: int, level: int,
                  bufs: "bam.BufferPool", molecular: bool = False, gz_device=None, fragment: Optional[str] = None,
                  marks: Optional[list] = None, first_key=(MINKEY, 0, 1), tie: int = 1, on_written=None,
-                 fq_device=None):
+                 fq_device=None, bam_device=None):
         self.fault, self.out_bam, self.fastq, self.header, self.prefix = fault, out_bam, fastq, header, prefix
         self.threads, self.level, self.bufs, self.molecular, self.gz_device = threads, level, bufs, molecular, gz_device
         self.fragment, self.first_key, self.tie, self.on_written = fragment, first_key, tie, on_written
         self.marks = [] if marks is None else marks
         self.fq_device, self.fastq_counters = fq_device, None
+        self.bam_device, self.bam_counters = bam_device, None
         self.T = {"records": 0.0, "encode": 0.0, "writer_wait": 0.0}
         self.records_out = 0
         self.outs, self.recq = queue.Queue(maxsize=1), queue.Queue(maxsize=1)  # consensus -> builder -> writer
@@ -318,7 +327,9 @@ class BackEnd(_Stages):
                 cons, chunk, cuts = item
                 t0 = time.perf_counter()
                 text = cons.fastq if self.fq_device is not None else None
-                if text is not None and self.out_bam is None:  # (the FASTQ pair reads no records)
+                brec = cons.bamrec if self.bam_device is not None else None
+                # (the FASTQ pair's device text reads no records, nor do the BAM's device records)
+                if (text is not None or self.fastq is None) and (brec is not None or self.out_bam is None):
                     recs, tags_buf = None, None
                 else:
                     recs, tags_buf = bam.duplex_records(cons, chunk.raw, self.prefix, self.threads,
@@ -326,7 +337,7 @@ class BackEnd(_Stages):
                 self.T["records"] += time.perf_counter() - t0
                 chunk.raw = chunk.plan = chunk.batches = None
                 del item, cons
-                self.recq.put((recs, tags_buf, chunk, cuts, text))
+                self.recq.put((recs, tags_buf, chunk, cuts, text, brec))
         except BaseException as e:  # noqa: BLE001
             self.fault(e)
             while self.outs.get() is not None:  # drain so that put() never blocks
@@ -340,7 +351,9 @@ class BackEnd(_Stages):
         try:
             gz = (lambda: bgzf.GpuBgzf(self.gz_device())) if self.gz_device is not None else (lambda: None)
             if self.out_bam is not None:  # (a GpuBgzf each: one job in flight)
-                w = bgzf.BamWriter(self.out_bam, bam.output_header(self.header), self.level, gz(), self.fragment)
+                w = bgzf.BamWriter(self.out_bam, bam.output_header(self.header), self.level,
+                                   bgzf.GpuBgzf(self.bam_device()) if self.bam_device is not None else gz(),
+                                   self.fragment)
             if self.fastq is not None:
                 fq = bgzf.FastqWriter(self.fastq[0], self.fastq[1], self.level,
                                       bgzf.GpuBgzf(self.fq_device()) if self.fq_device is not None else gz(),
@@ -350,16 +363,18 @@ class BackEnd(_Stages):
                 item = self.recq.get()
                 if item is None:
                     break
-                recs, tags_buf, chunk, cuts, text = item
+                recs, tags_buf, chunk, cuts, text, brec = item
                 t1 = time.perf_counter()
                 a = 0
-                n_out = recs.n if recs is not None else 2 * sum(x.kept for x in text)
+                n_out = recs.n if recs is not None else 2 * sum(x.kept for x in (text if text is not None else brec))
                 part = None
                 for idx, key in cuts + [(n_out, None)]:
                     if recs is not None:
                         part = recs if (a == 0 and idx == n_out) else _slice_records(recs, a, idx)
                     if idx > a:
-                        if w is not None:
+                        if w is not None and brec is not None:
+                            w.add_device([_rec_ranges(brec, a // 2, idx // 2)], th)
+                        elif w is not None:
                             w.add(part, th)
                         if fq is not None and text is not None:
                             fq.add_device(_text_ranges(text, a // 2, idx // 2), th)
@@ -372,7 +387,7 @@ class BackEnd(_Stages):
                     a = idx
                 self.records_out += n_out
                 self.T["encode"] += time.perf_counter() - t1
-                del item, recs, part, text  # (the device text is released here, the job that reads it submitted)
+                del item, recs, part, text, brec  # (the device bytes are released here, the job that reads them submitted)
                 # (the chunk's records are written; nothing refers to their arrays)
                 self.bufs.give(chunk.pool_buf)
                 self.bufs.give(tags_buf)
@@ -380,6 +395,11 @@ class BackEnd(_Stages):
                     self.on_written(chunk)
             if w is not None:
                 w.close(th)
+                if self.bam_device is not None:
+                    c = w.gpu.counters()
+                    self.bam_counters = {"blocks": c["blocks"], "raw_bytes": c["text_bytes"],
+                                         "compressed_bytes": c["compressed_bytes"],
+                                         "fallback_blocks": c["fallback_blocks"]}
             if fq is not None:
                 fq.close(th)
                 if self.fq_device is not None:
@@ -403,13 +423,15 @@ def step5_stream(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, p
                  chunk_bytes: int = bam.DEFAULT_CHUNK_BYTES, slack: int = bam.DEFAULT_SLACK,
                  batch_bases: Optional[int] = None, stats: Optional[dict] = None, gpu_bgzf: bool = False,
                  defer: Optional[int] = None, read_size: int = 8 << 20, filter=None, gpu_inflate: bool = False,
-                 gpu_fastq: bool = False) -> dict:
+                 gpu_fastq: bool = False, gpu_bam: bool = False) -> dict:
     """step5 in bounded memory, pipelined (run); defer: the span past which a template is
     deferred (default DEFAULT_DEFER_SPAN; 0 = off); read_size: compressed bytes per refill;
     filter: as step5's; gpu_inflate: the input's BGZF blocks inflate on the GPU (bgzf.GpuInflate);
-    gpu_fastq: the FASTQ pair is formatted, checksummed and deflated on the GPU (StreamJob)."""
+    gpu_fastq: the FASTQ pair is formatted, checksummed and deflated on the GPU (StreamJob);
+    gpu_bam: the BAM's records are written, checksummed and deflated on the GPU (StreamJob)."""
     job = StreamJob(in_bam, fasta, out_bam, fastq, prefix, threads, level, tags, gpu_bgzf, chunk_bytes, slack,
-                    batch_bases, read_size, filter=filter, defer=defer, gpu_inflate=gpu_inflate, gpu_fastq=gpu_fastq)
+                    batch_bases, read_size, filter=filter, defer=defer, gpu_inflate=gpu_inflate, gpu_fastq=gpu_fastq,
+                    gpu_bam=gpu_bam)
     return _public(run(job, engine, stats=stats))
 
 
@@ -417,7 +439,7 @@ def molecular_stream(in_bam: str, out_bam: Optional[str], engine=None, prefix: O
                      level: int = 6, fastq: Optional[Tuple[str, str]] = None, tags: bool = True,
                      chunk_bytes: int = bam.DEFAULT_CHUNK_BYTES, batch_bases: Optional[int] = None,
                      stats: Optional[dict] = None, gpu_bgzf: bool = False, min_consensus_base_quality: int = 0,
-                     filter=None, gpu_inflate: bool = False, gpu_fastq: bool = False) -> dict:
+                     filter=None, gpu_inflate: bool = False, gpu_fastq: bool = False, gpu_bam: bool = False) -> dict:
     """Rule call_consensus_reads_molecular (main.snake.py:46-55) in bounded memory: the same
     pipeline as step5_stream over a GroupReadsByUmi-ordered input cut between MI runs
     (stream_chunks(runs=True)); each chunk's runs are its consensus families (pipeline.molecular_records,
@@ -426,7 +448,7 @@ def molecular_stream(in_bam: str, out_bam: Optional[str], engine=None, prefix: O
     (main.snake.py:54, README.md:83); this holds about six chunks."""
     job = StreamJob(in_bam, None, out_bam, fastq, prefix, threads, level, tags, gpu_bgzf, chunk_bytes,
                     batch_bases=batch_bases, molecular=int(min_consensus_base_quality), filter=filter,
-                    gpu_inflate=gpu_inflate, gpu_fastq=gpu_fastq)
+                    gpu_inflate=gpu_inflate, gpu_fastq=gpu_fastq, gpu_bam=gpu_bam)
     return _public(run(job, engine, stats=stats))
 
 
@@ -493,6 +515,19 @@ def _text_ranges(text, a: int, b: int) -> list:
         if hi > lo:
             for d, r in enumerate(x.ranges(lo, hi)):
                 out[d] += r
+        k0 += x.kept
+    return out
+
+
+def _rec_ranges(brec, a: int, b: int) -> list:
+    """Kept families a..b-1 of a chunk whose batches' device records are `brec` (pipeline.BamPiece
+    each, in order) -> the BAM's byte ranges in order (BamWriter.add_device's pieces[0]); output
+    record k is record k & 1 of kept family k // 2."""
+    out, k0 = [], 0
+    for x in brec:
+        lo, hi = max(a - k0, 0), min(b - k0, x.kept)
+        if hi > lo:
+            out += x.ranges(lo, hi)
         k0 += x.kept
     return out
 
@@ -567,10 +602,16 @@ def _run_chunk(eng, runner, ch: Chunk, mode: int, tags: bool, job: StreamJob, G:
     if ch.batches is None:
         return pipeline.run_step5(eng, ch.raw, tags=tags, batch_bases=job.batch_bases, filter=job.filter)[0]
     fkw = {} if job.filter is None else {"filter": job.filter, "molecular": job.molecular is not None}
-    if job.gpu_fastq:  # the batches' FASTQ text is made where their consensus lies; no BAM: the bases stay there
-        raw = ch.raw
-        fkw.update(fastq_names=lambda fb: bam.family_names(fb.fam_mi, raw.mi_names, job.prefix),
-                   seqqual=job.out_bam is not None)
+    raw = ch.raw
+    names = lambda fb: bam.family_names(fb.fam_mi, raw.mi_names, job.prefix)  # noqa: E731
+    # an output formatted on the host reads the fetched bases: the BAM without gpu_bam, the pair without gpu_fastq
+    host_out = (job.out_bam is not None and not job.gpu_bam) or (job.fastq is not None and not job.gpu_fastq)
+    if job.gpu_fastq:  # the batches' FASTQ text is made where their consensus lies
+        fkw.update(fastq_names=names, seqqual=host_out)
+    if job.gpu_bam:  # so are the BAM's records; the tags' rows then stay in HBM
+        fkw.update(bam_tables=lambda fb: (names(fb), bam.family_aux(fb.fam_off, fb.src, fb.fam_mi, raw, job.threads)),
+                   bam_tags=job.tags, seqqual=host_out, molecular=job.molecular is not None)
+        tags = False
     return pipeline.concat_consensus(pipeline.run_batches(eng, ch.batches, mode, tags, G, **fkw))
 
 
@@ -599,11 +640,13 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
         eng = Engine(0) if own else engine
     else:
         eng = None
-        if job.gpu_bgzf or molecular or job.filter is not None or job.gpu_inflate or job.gpu_fastq:
+        if job.gpu_bgzf or molecular or job.filter is not None or job.gpu_inflate or job.gpu_fastq or job.gpu_bam:
             raise ValueError("a runner stream: step 5 with host inflate and deflate only, unfiltered "
-                             "(no gpu_bgzf, gpu_inflate or gpu_fastq)")
+                             "(no gpu_bgzf, gpu_inflate, gpu_fastq or gpu_bam)")
     if job.gpu_fastq and job.fastq is None:
         raise ValueError("gpu_fastq needs the FASTQ pair (fastq=(path1, path2))")
+    if job.gpu_bam and job.out_bam is None:
+        raise ValueError("gpu_bam needs the output BAM (out_bam)")
     out_bam, fastq = job.out_bam, job.fastq
     info = {"records_in": 0, "families": 0, "families_emitted": 0, "records_out": 0, "chunks": 0,
             "spilled_bytes": 0, "deferred_families": 0, "splices": []}
@@ -654,7 +697,8 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
                        (lambda: eng.device) if job.gpu_bgzf else None,
                        "first" if (solo and dspan) else job.fragment, marks, k_first,
                        tie=0 if late is not None else 1,  # (a spill piece sorts before the stream's piece of its key)
-                       fq_device=(lambda: eng.device) if job.gpu_fastq else None)
+                       fq_device=(lambda: eng.device) if job.gpu_fastq else None,
+                       bam_device=(lambda: eng.device) if job.gpu_bam else None)
         pjob = dataclasses.replace(job, prefix=prefix)  # (the read names' prefix, resolved)
         mode = pipeline.MODE_VOTE if molecular else pipeline.MODE_CONVERT | pipeline.MODE_EXTEND | pipeline.MODE_VOTE
         tg = job.tags and out_bam is not None  # the FASTQ pair carries no tags
@@ -688,6 +732,8 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
         if not fault.errors:
             if job.gpu_fastq:
                 info["gpu_fastq"] = back.fastq_counters
+            if job.gpu_bam:
+                info["gpu_bam"] = back.bam_counters
             info["records_out"] = back.records_out
             info["spilled_bytes"] = front.spilled_bytes
             info["deferred_families"] = int(rs.get("deferred", 0))
@@ -738,6 +784,8 @@ def _finish_deferred(job: StreamJob, eng, runner, marks, spill_path: str, info: 
             info[k] += inf2[k]
         if "gpu_fastq" in inf2:
             info["gpu_fastq"] = {k: v + inf2["gpu_fastq"][k] for k, v in info["gpu_fastq"].items()}
+        if "gpu_bam" in inf2:
+            info["gpu_bam"] = {k: v + inf2["gpu_bam"][k] for k, v in info["gpu_bam"].items()}
         if "gpu_inflate" in inf2:  # (the spill's BAM, inflated the same way)
             info["gpu_inflate_deferred"] = inf2["gpu_inflate"]
         if job.filter is not None:

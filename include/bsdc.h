@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BSDC_ABI_VERSION 18
+#define BSDC_ABI_VERSION 19
 #define BSDC_SMALL_BUCKETS 8
 #define BSDC_LARGE_BUCKETS 6
 #define BSDC_LARGE_LDS_MAX 158912 /* LDS arena bytes one large-family workgroup may use */ /* LDS arena size classes of the wavefront-per-family kernel */
@@ -357,6 +357,37 @@ int32_t bsdc_fastq_format(const bsdc_consensus *out, const uint8_t *filt, int64_
  * block; what bsdc_bgzf_sink_put of libbsdc_io takes as the blocks' crc[].  A file's short last
  * block stays with the host.  Device pointers, `in` 16-byte aligned; enqueued on `stream`. */
 int32_t bsdc_bgzf_crc32(const uint8_t *in, int64_t blk0, int64_t nblk, uint32_t *crc, void *stream);
+
+/* (ABI 19) The output BAM's records written on the device (replaces the record encoder of fgbio's /
+ * htsjdk's BAM writer behind CallDuplexConsensusReads / CallMolecularConsensusReads --output,
+ * main.snake.py:46-55,155-164, and the host writer's tag and encode passes; csrc/bsdc_bam.hip,
+ * DESIGN.md section 8.8).  `out` is the bsdc_consensus the vote filled (seq, qual and, with_tags,
+ * the ss_* rows 4-byte aligned) and filt the filter's output or NULL: family f is written when
+ * status[f] & 1 and (filt NULL or filt[f] == 0).  kind: 0 duplex, 1 molecular, as bsdc_filter's.
+ * name_off / name_buf and aux_off / aux_buf: packed tables [n_fam + 1], one read name (at most 253
+ * bytes) and one run of aux bytes (RG / MI / RX, both mates alike; at most 1 MiB) per family; the
+ * *_host arguments are the caller's host copies of the offsets, which are what gets checked.
+ * off [n_fam + 1] receives the exclusive prefix sum of the families' byte counts (off[n_fam] = the
+ * total, true whatever cap is) and rec + off[f] the family's records R1, R2, each what libbsdc_io
+ * encodes for it: block_size; tid -1, pos -1, l_read_name, mapq 0, bin 4680, no cigar, flag 77 /
+ * 141, l_seq = len[2f + e], next -1 / -1, tlen 0; name NUL; (l_seq + 1) / 2 bytes of row (f, e) of
+ * out->seq, the pad nibble of an odd length 0; l_seq QUAL bytes; the aux bytes; with_tags the bytes
+ * of libbsdc_io's bsdc_consensus_tags for the record (kind 0: cD cM cE aD aM aE [bD bM bE] ad ae ac
+ * aq [bd be bc bq]; kind 1: cD cM cE cd ce; rows cut to l_seq; integers in the smallest BAM type;
+ * a read without depth gets the 0 / 0 of the host that launches).  No byte at or past rec + cap is
+ * written.  bsdc_bam_bytes_bound = a size known before the launch (name_bytes, aux_bytes: the
+ * tables' sizes), < 0 on bad arguments; tmp: bsdc_bam_tmp_bytes of 8-byte aligned scratch.
+ * Everything is enqueued on `stream` by the one call, after the vote and the filter on it; device
+ * pointers but for `out` itself and the two *_host copies.  BSDC_EINVAL, before any device is
+ * touched: a NULL pointer (filt apart), a negative count or cap, offsets that go backwards, a name
+ * over 253 bytes, with_tags with out->ss_* NULL, kind outside 0 / 1. */
+int64_t bsdc_bam_bytes_bound(int64_t n_fam, int64_t name_bytes, int64_t aux_bytes, int32_t stride, int32_t kind,
+                             int32_t with_tags);
+int64_t bsdc_bam_tmp_bytes(int64_t n_fam);
+int32_t bsdc_bam_format(const bsdc_consensus *out, const uint8_t *filt, int32_t kind, int32_t with_tags, int64_t n_fam,
+                        const int64_t *name_off, const uint8_t *name_buf, const int64_t *name_off_host,
+                        const int64_t *aux_off, const uint8_t *aux_buf, const int64_t *aux_off_host, int64_t *off,
+                        uint8_t *rec, int64_t cap, uint8_t *tmp, void *stream);
 
 #ifdef __cplusplus
 }
