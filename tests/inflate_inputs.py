@@ -3,6 +3,8 @@ each with the isize and the bytes it promises.  Valid ones come from Python's zl
 from the small assembler below where zlib's deflate never writes the case (distance 32768, chosen
 repeat codes); corrupt ones are valid ones with bits edited, one per status code, each of which
 zlib rejects too (or inflates to another size than the isize claimed).  `ref()` is zlib's answer.
+Behind them the edge lists -- copies(), rounds(), tables(), placements(), flips() -- for what the
+kernel's 64 lanes do that the twin's one lane does not (the section's header says which).
 """
 from __future__ import annotations
 
@@ -61,6 +63,9 @@ class BitW:
         if self.n:
             self.put(0, 8 - self.n)
 
+    def nbits(self) -> int:  # the bits written so far
+        return 8 * len(self.out) + self.n
+
     def bytes(self) -> bytes:
         self.align()
         return bytes(self.out)
@@ -111,7 +116,8 @@ CL_ORDER = [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15]
 
 def put_tokens(w: BitW, toks, lit_lens, dist_lens):
     """tokens: ("L", byte) | ("M", length, distance) | ("E",) end of block | ("S", lit/len symbol)
-    | ("D", length, distance symbol, extra bits' value): a raw symbol."""
+    | ("D", length, distance symbol, extra bits' value): a raw symbol
+    | ("X", length symbol, its extra bits' value, distance symbol, its extra bits' value)."""
     lc, dc = canon(lit_lens), canon(dist_lens)
 
     def sym(s):
@@ -136,6 +142,12 @@ def put_tokens(w: BitW, toks, lit_lens, dist_lens):
             assert dist_lens[k]
             w.code(dc[k], dist_lens[k])
             w.put(t[2] - DIST_BASE[k], DIST_EXTRA[k])
+        elif t[0] == "X":
+            sym(t[1])
+            w.put(t[2], LEN_EXTRA[t[1] - 257])
+            assert dist_lens[t[3]], t[3]
+            w.code(dc[t[3]], dist_lens[t[3]])
+            w.put(t[4], DIST_EXTRA[t[3]])
         else:
             length(t[1])
             w.code(dc[t[2]], dist_lens[t[2]])
@@ -374,4 +386,555 @@ def corrupt() -> List[Block]:
     w.put(1, 1)  # the distance code's unused bit
     w.put(0, 16)
     add("unused_distance_code", w.bytes(), 6, L.INFLATE_ECODE)
+    return out
+
+
+# ---- edge lists (tests/test_inflate_edges.py, tests/test_gpu_inflate_edges.py) ------------------
+# Hand-assembled blocks for what the kernel runs differently from its host twin (64 lanes against
+# one) or where the twin has no counterpart: copy_match's (distance, length) grid, the 256-token
+# ring, the 2 KiB compressed window, huff_build across lanes, the write-out's alignments, and every
+# single-bit flip of four small streams.  Every valid block's bytes are zlib's, and the plain
+# decoder `trace` below (bit at a time, no tables) says what each fixture holds, so that one that
+# drifts from its edge fails where it is built.
+ANY = -1  # Block.code of a flipped stream zlib rejects: any nonzero status
+
+
+def trace(comp: bytes):
+    """(deflate blocks, bytes): per deflate block its type, the lit/len and distance lengths and its
+    tokens (first bit, bit after, length or None for a literal, distance, the lit/len code's bits,
+    the distance code's bits), the end-of-block code not among them.  For valid streams only."""
+    pos = 0
+
+    def bits(n):
+        nonlocal pos
+        v = 0
+        for i in range(n):
+            v |= ((comp[pos >> 3] >> (pos & 7)) & 1) << i
+            pos += 1
+        return v
+
+    def table(lens):
+        return {(n, c): s for s, (n, c) in enumerate(zip(lens, canon(lens))) if n}
+
+    def sym(t):
+        c = n = 0
+        while (n, c) not in t:
+            c, n = c << 1 | bits(1), n + 1
+            assert n <= 15
+        return t[(n, c)], n
+
+    blocks, out = [], bytearray()
+    while True:
+        final, typ = bits(1), bits(2)
+        blk = dict(type=typ, at=pos - 3, tokens=[], lit=None, dist=None)
+        blocks.append(blk)
+        if typ == 0:
+            pos = (pos + 7) & ~7
+            n = bits(16)
+            assert bits(16) == n ^ 0xFFFF
+            out += comp[pos >> 3:(pos >> 3) + n]
+            pos += 8 * n
+        else:
+            assert typ in (1, 2)
+            lit, dist = FIXED_LIT, FIXED_DIST
+            if typ == 2:
+                hlit, hdist, hclen = bits(5) + 257, bits(5) + 1, bits(4) + 4
+                cl = [0] * 19
+                for k in range(hclen):
+                    cl[CL_ORDER[k]] = bits(3)
+                ct, lens, blk["cl_syms"] = table(cl), [], []
+                while len(lens) < hlit + hdist:
+                    s, _ = sym(ct)
+                    blk["cl_syms"].append(s)
+                    if s < 16:
+                        lens.append(s)
+                    else:
+                        lens += [lens[-1] if s == 16 else 0] * ({16: 3, 17: 3, 18: 11}[s] + bits({16: 2, 17: 3, 18: 7}[s]))
+                assert len(lens) == hlit + hdist
+                lit, dist = lens[:hlit], lens[hlit:]
+                blk["hclen"], blk["header_bits"] = hclen, pos - blk["at"]
+            blk["lit"], blk["dist"] = list(lit), list(dist)
+            lt, dt = table(lit), table(dist)
+            while True:
+                a = pos
+                s, n1 = sym(lt)
+                if s == 256:
+                    break
+                if s < 256:
+                    out.append(s)
+                    blk["tokens"].append((a, pos, None, 0, n1, 0))
+                else:
+                    ln = LEN_BASE[s - 257] + bits(LEN_EXTRA[s - 257])
+                    ds, n2 = sym(dt)
+                    d = DIST_BASE[ds] + bits(DIST_EXTRA[ds])
+                    assert d <= len(out)
+                    for _ in range(ln):
+                        out.append(out[-d])
+                    blk["tokens"].append((a, pos, ln, d, n1, n2))
+        if final:
+            return blocks, bytes(out)
+
+
+def _finish(out: List[Block], name: str, comp: bytes, isize_max: int = 65536):
+    """a valid block: zlib's bytes, which the plain decoder agrees with; returns its trace"""
+    want = ref(comp)
+    blocks, got = trace(comp)
+    assert got == want and len(want) <= isize_max, name
+    out.append(Block(name, comp, len(want), want))
+    return blocks
+
+
+def _lits(rng, n, lo=0, hi=256):
+    return [("L", int(x)) for x in rng.integers(lo, hi, n)]
+
+
+def _bytes(rng, n) -> bytes:
+    return rng.integers(0, 256, n, dtype=np.uint8).tobytes()
+
+
+COPY_D = (1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 66, 127, 128, 129, 191, 192, 193, 255, 256, 257,
+          258, 259, 260)
+COPY_LEN = (3, 4, 5, 31, 32, 33, 63, 64, 65, 66, 127, 128, 129, 130, 191, 192, 193, 257, 258)
+
+
+@functools.lru_cache(maxsize=None)
+def copies() -> List[Block]:
+    """fixed-Huffman blocks: every (distance, length) of COPY_D x COPY_LEN after a random prefix, a
+    literal before every second match only (the others read the match before them, in the same
+    ring); then single cases at the copy's edges."""
+    out: List[Block] = []
+    rng = _rng(6)
+    pairs = [(d, n) for n in COPY_LEN for d in COPY_D]
+    pairs = [pairs[int(k)] for k in rng.permutation(len(pairs))]
+    seen, toks, size = set(), None, 0
+
+    def flush():
+        w = BitW()
+        fixed_block(w, toks + [("E",)])
+        for t in _finish(out, "grid_%d" % len(out), w.bytes())[0]["tokens"]:
+            if t[2]:
+                seen.add((t[3], t[2]))
+
+    for k, (d, n) in enumerate(pairs):
+        if toks is None or size + n + 1 > 65536:
+            if toks:
+                flush()
+            toks, size = _lits(rng, 260), 260
+        if k % 2 == 0:
+            toks += _lits(rng, 1)
+            size += 1
+        toks.append(("M", n, d))
+        size += n
+    flush()
+    assert seen == set(pairs) and len(pairs) == 570  # the grid is in the streams, pair for pair
+    for d in (1, 2, 3, 63, 64, 65, 258, 260):  # the first position that allows the distance
+        w = BitW()
+        fixed_block(w, _lits(rng, d) + [("M", 258, d), ("M", 3, 258 + d), ("E",)])
+        t = _finish(out, "pos_eq_d_%d" % d, w.bytes())[0]["tokens"]
+        assert t[d][2:4] == (258, d) and len(t) == d + 2
+    for name, ls, le in (("len_258_symbol_285", 285, 0), ("len_258_symbol_284_extra_31", 284, 31)):
+        for ds in (0, 2, 12):  # distances 1, 3 and 65
+            w = BitW()
+            fixed_block(w, _lits(rng, 70) + [("X", ls, le, ds, 0), ("L", 9), ("X", ls, le, ds, 0), ("E",)])
+            t = _finish(out, "%s_d%d" % (name, DIST_BASE[ds]), w.bytes())[0]["tokens"]
+            assert t[70][2:4] == (258, DIST_BASE[ds]) and t[70][1] - t[70][0] == (13 if ls == 285 else 18) + DIST_EXTRA[ds]
+    for name, head, tail in (("ends_at_65536_with_a_match", 4, []), ("ends_at_65535_with_a_literal", 3, [("L", 200)])):
+        tk = _lits(rng, head)
+        for k in range(254):
+            tk.append(("M", 258, min(COPY_D[(7 * k) % len(COPY_D)], head + 258 * k)))
+        w = BitW()
+        fixed_block(w, tk + tail + [("E",)])
+        t = _finish(out, name, w.bytes())[0]["tokens"]
+        assert out[-1].isize == 65536 and (t[-1][2] == 258 if not tail else t[-1][2] is None)
+    return out
+
+
+RING = 256  # inf::kTok
+
+
+def _ring_tokens(rng, n, shape, pos):
+    """n tokens of a shape after `pos` bytes of output: lengths 3..100, any distance the position allows"""
+    toks = []
+    for k in range(n):
+        if shape == "literals" or (shape == "alternating" and k % 2 == 0):
+            toks += _lits(rng, 1)
+            pos += 1
+        else:
+            ln = int(rng.integers(3, 101))
+            toks.append(("M", ln, int(rng.integers(1, min(pos, 400) + 1))))
+            pos += ln
+    return toks, pos
+
+
+def _rle(lens, use_17=True, use_16=False):
+    """the lengths as code-length symbols: zero runs by 18 (and 17), equal runs by 16 when asked"""
+    seq, i = [], 0
+    while i < len(lens):
+        j = i
+        while j < len(lens) and lens[j] == lens[i]:
+            j += 1
+        run = j - i
+        if lens[i] == 0 and run >= 11:
+            run = min(run, 138)
+            seq.append((18, run - 11))
+        elif lens[i] == 0 and run >= 3 and use_17:
+            run = min(run, 10)
+            seq.append((17, run - 3))
+        elif lens[i] and run >= 4 and use_16:
+            run = min(run, 7)
+            seq += [(lens[i], 0), (16, run - 4)]
+        else:
+            run = 1
+            seq.append((lens[i], 0))
+        i += run
+    return seq
+
+
+def _costliest_block() -> bytes:
+    """the most compressed bytes one token round can consume within an isize of 65536: after 24577
+    stored bytes, 256 tokens of 48 bits (15-bit codes for length symbol 281 and distance symbol 29,
+    5 + 13 extra bits), then length-3 tokens of 43 bits (15-bit codes for 257 and 28 / 29) to the
+    end.  The code-length code is given (fifteen 4-bit codes, two of 5 bits): a Huffman code over
+    this header's few symbols would pass 7 bits."""
+    rng = _rng(7)
+    w = BitW()
+    stored_block(w, _bytes(rng, 24577), final=False)
+    lit, dist = [0] * 282, [0] * 30
+    for s in range(13):
+        lit[s] = s + 1
+    lit[256], lit[257], lit[281] = 14, 15, 15
+    for s in range(14):
+        dist[s] = s + 1
+    dist[28] = dist[29] = 15
+    cl_lens = [4] * 16 + [0, 0, 4]
+    cl_lens[14] = cl_lens[15] = 5
+    lens = [int(x) for x in rng.integers(131, 163, RING)]
+    body = 65534 - 24577
+    while (body - sum(lens)) % 3:
+        lens[-1] = 131 + (lens[-1] - 130) % 32
+    toks, pos = [], 24577
+    for ln in lens:
+        toks.append(("X", 281, ln - 131, 29, int(rng.integers(0, min(8191, pos - 24577) + 1))))
+        pos += ln
+    while pos < 65534:
+        ds = 28 + int(rng.integers(0, 2))
+        toks.append(("X", 257, 0, ds, int(rng.integers(0, 8192))))
+        pos += 3
+    dynamic_block(w, lit, dist, toks + [("E",)], cl_seq=_rle(lit + dist, use_17=False), cl_lens=cl_lens)
+    return w.bytes()
+
+
+@functools.lru_cache(maxsize=None)
+def rounds() -> List[Block]:
+    """the token ring's boundaries: 255, 256, 257, 511, 512 and 513 tokens before the end-of-block
+    code (last in a ring, alone in the next, second in the next), all literals / all matches /
+    alternating, as the final deflate block and before another; matches that read the same ring's
+    literals and the ring before's last match; the costliest round."""
+    out: List[Block] = []
+    for n in (255, 256, 257, 511, 512, 513):
+        for shape in ("literals", "matches", "alternating"):
+            for final in (True, False):
+                rng = _rng(8, n, len(shape), final)
+                w = BitW()
+                stored_block(w, _bytes(rng, 401), final=False)
+                toks, pos = _ring_tokens(rng, n, shape, 401)
+                fixed_block(w, toks + [("E",)], final=final)
+                if not final:
+                    fixed_block(w, _ring_tokens(rng, 7, "alternating", pos)[0] + [("E",)])
+                b = _finish(out, "%d_%s_%s" % (n, shape, "final" if final else "then_more"), w.bytes())
+                assert [len(x["tokens"]) for x in b] == [0, n] + [7] * (not final)
+                k = sum(t[2] is not None for t in b[1]["tokens"])
+                assert k == {"literals": 0, "matches": n, "alternating": n // 2}[shape]
+    rng = _rng(9)
+    for d, ln in ((1, 70), (2, 130), (1, 258)):  # token 256 reads literal token 255 of its ring
+        w = BitW()
+        fixed_block(w, _lits(rng, RING - 1) + [("M", ln, d)] + _lits(rng, 3) + [("M", 5, 4), ("E",)])
+        t = _finish(out, "token_256_reads_token_255_d%d_len%d" % (d, ln), w.bytes())[0]["tokens"]
+        assert t[RING - 1][2:4] == (ln, d) and t[RING - 2][2] is None
+    for ln0, d, ln in ((40, 40, 100), (200, 1, 3), (258, 130, 258), (3, 3, 200)):
+        # the next ring's first token reads the bytes of the ring's last token, a match
+        w = BitW()
+        fixed_block(w, _lits(rng, RING - 1) + [("M", ln0, 200), ("M", ln, d)] + _lits(rng, 2) + [("E",)])
+        t = _finish(out, "ring_reads_last_match_of_ring_before_%d_%d_%d" % (ln0, d, ln), w.bytes())[0]["tokens"]
+        assert t[RING - 1][2:4] == (ln0, 200) and t[RING][2:4] == (ln, d) and d <= ln0
+    b = _finish(out, "costliest_round", _costliest_block(), 65534)
+    t = b[1]["tokens"]
+    assert out[-1].isize == 65534 and b[0]["type"] == 0 and len(t) > 1000
+    assert all(x[1] - x[0] == 48 and 131 <= x[2] <= 162 and x[3] >= 24577 for x in t[:RING])
+    assert t[RING - 1][1] - t[0][0] == 8 * 1536  # the first ring's compressed bytes
+    assert all(x[1] - x[0] == 43 and x[2] == 3 for x in t[RING:])
+    return out
+
+
+def trace_hclen(comp: bytes) -> int:
+    """the code-length codes a first dynamic block's header announces"""
+    assert comp[0] & 6 == 4
+    return ((comp[0] | comp[1] << 8 | comp[2] << 16) >> 13 & 15) + 4
+
+
+def _skewed():
+    """sixteen symbols' lengths 1, 2, ..., 14, 15, 15: complete, every length 1..15 present"""
+    return list(range(1, 15)) + [15, 15]
+
+
+def _largest_header(w: BitW, toks, final=True):
+    """HLIT 286 + HDIST 30 = 316 lengths, every one written singly with a 7-bit code of the
+    code-length code (lengths 8 and 9, 4 and 5; its shorter codes go to symbols no length uses)"""
+    cl_lens = [0] * 19
+    for s, n in ((0, 1), (1, 2), (2, 3), (3, 4), (6, 5), (4, 7), (5, 7), (8, 7), (9, 7)):
+        cl_lens[s] = n
+    lit, dist = [8] * 226 + [9] * 60, [4] * 2 + [5] * 28
+    dynamic_block(w, lit, dist, toks, cl_lens=cl_lens, final=final)
+    return lit, dist
+
+
+def _largest_header_block() -> bytes:
+    rng = _rng(10)
+    w = BitW()
+    fixed_block(w, _lits(rng, 301, 144, 256) + [("E",)], final=False)  # more than a ring of 9-bit codes, an odd bit count
+    _largest_header(w, _lits(rng, 40) + [("M", 258, 33), ("M", 100, 301), ("E",)])
+    return w.bytes()
+
+
+@functools.lru_cache(maxsize=None)
+def tables() -> List[Block]:
+    """dynamic headers at huff_build's and step_header's edges.  Three entries are corrupt on
+    purpose, each because RFC 1951 leaves no valid block of the shape asked for; zlib rejects
+    them too (tests/test_inflate_edges.py asserts it):
+      - HCLEN of 4 codes: only 16, 17, 18 and 0 get a code, so no length but 0 can be written and
+        the end-of-block code has none (ENOEOB); the smallest valid one has 5 (all lengths 8);
+      - an 18-run of 138 across the HLIT / HDIST boundary covers symbol 256 (ENOEOB); the longest
+        valid one has 29 + 29 zeros behind symbol 256;
+      - the unused bit of a one-bit distance code after a block whose distance table had long
+        codes: there is no valid use of "no code" (ECODE)."""
+    out: List[Block] = []
+    rng = _rng(11)
+
+    def bad(name, comp, isize, code):
+        try:
+            assert len(ref(comp)) != isize, name
+        except zlib.error:
+            pass
+        out.append(Block(name, comp, isize, None, code))
+
+    # every symbol coded; lengths through 284 + 31 and 285, distance 32768 through symbol 29's extra bits set
+    w = BitW()
+    stored_block(w, _bytes(rng, 32768), final=False)
+    lit, dist = [8] * 226 + [9] * 60, [4] * 2 + [5] * 28
+    toks = [("X", 285, 0, 29, 8191), ("X", 284, 31, 29, 8191)]
+    for k in range(30):
+        ls = 257 + (k % 29)
+        toks += _lits(rng, 2) + [("X", ls, (1 << LEN_EXTRA[ls - 257]) - 1, k, (1 << DIST_EXTRA[k]) - 1)]
+    dynamic_block(w, lit, dist, toks + [("E",)])
+    b = _finish(out, "hlit_286_hdist_30_all_coded", w.bytes())
+    assert len(b[1]["lit"]) == 286 and len(b[1]["dist"]) == 30 and all(b[1]["lit"]) and all(b[1]["dist"])
+    assert [t[2:4] for t in b[1]["tokens"][:2]] == [(258, 32768)] * 2 and b[1]["tokens"][-1][3] == 32768
+
+    # a literal table with every length 1..15 (the fast table and the canonical path, every length of it)
+    lit = [0] * 257
+    for s, n in zip(list(range(65, 80)) + [256], _skewed()):
+        lit[s] = n
+    w = BitW()
+    dynamic_block(w, lit, [1], _lits(rng, 400, 65, 80) + [("L", s) for s in range(65, 80)] + [("E",)],
+                  cl_seq=_rle(lit + [1]))
+    b = _finish(out, "literal_lengths_1_to_15", w.bytes())
+    assert {t[4] for t in b[0]["tokens"]} == set(range(1, 16))
+
+    # distance codes of 10 to 15 bits in use (symbols 9..15: distances 25..255)
+    dist = list(range(1, 10)) + [10, 11, 12, 13, 14, 15, 15]
+    lit = [8] * 254 + [9] * 4  # 254 / 256 + 4 / 512 = 1; 257 is the only length symbol (length 3)
+    toks = _lits(rng, 300, 0, 254)
+    for k in range(40):
+        ds = 9 + k % 7
+        toks += [("X", 257, 0, ds, int(rng.integers(0, 1 << DIST_EXTRA[ds])))] + _lits(rng, k % 2, 0, 254)
+    w = BitW()
+    dynamic_block(w, lit, dist, toks + [("E",)], cl_seq=_rle(lit + dist, use_16=True))
+    b = _finish(out, "distance_codes_10_to_15_bits", w.bytes())
+    assert {t[5] for t in b[0]["tokens"] if t[2]} == set(range(10, 16))  # longer than the 9-bit table, decoded
+
+    # one distance code of one bit, in use (incomplete, accepted): as symbol 0 and as symbol 1
+    for name, dist in (("one_distance_code_symbol_0", [1]), ("one_distance_code_symbol_1", [0, 1])):
+        lit = [0] * 258
+        for s in (97, 98, 256, 257):
+            lit[s] = 2
+        w = BitW()
+        dynamic_block(w, lit, dist, [("L", 97), ("L", 98), ("X", 257, 0, len(dist) - 1, 0)] * 30 + [("E",)],
+                      cl_seq=_rle(lit + dist))
+        b = _finish(out, name, w.bytes())
+        assert sum(b[0]["dist"]) == 1 and sum(t[2] is not None for t in b[0]["tokens"]) == 30
+
+    # no distance code at all, literals only
+    lit = [0] * 257
+    for s in (97, 98, 99, 256):
+        lit[s] = 2
+    w = BitW()
+    dynamic_block(w, lit, [0], _lits(rng, 700, 97, 100) + [("E",)], cl_seq=_rle(lit + [0]))
+    b = _finish(out, "no_distance_code", w.bytes())
+    assert b[0]["dist"] == [0]
+
+    # the shortest code-length code: 4 codes cannot be valid (see above), 5 can (every length 8)
+    w = BitW()
+    dynamic_block(w, [0] * 257, [0], [], cl_seq=[(18, 127), (18, 109)], cl_lens=[1] + [0] * 17 + [1])
+    w.put(0, 16)
+    assert trace_hclen(w.bytes()) == 4
+    bad("hclen_4_has_no_end_of_block", w.bytes(), 1, L.INFLATE_ENOEOB)
+    lit = [8] * 255 + [0, 8]
+    w = BitW()
+    dynamic_block(w, lit, [0], _lits(rng, 500, 0, 255) + [("E",)], cl_seq=[(8, 0)] * 255 + [(0, 0), (8, 0), (0, 0)],
+                  cl_lens=[1, 0, 0, 0, 0, 0, 0, 0, 1] + [0] * 10)
+    b = _finish(out, "hclen_5", w.bytes())
+    assert b[0]["hclen"] == 5
+
+    # HCLEN 19 with all nineteen code-length symbols in the header
+    lit = [0] * 261  # (a single zero at 13, 241 zeros for 18, three behind 257 for 17, the 5s for 16)
+    for s in range(13):
+        lit[s] = s + 1
+    lit[14], lit[256], lit[257] = 14, 15, 15
+    dist = [4] * 2 + [5] * 28
+    cl_lens = [4] * 13 + [5] * 6
+    w = BitW()
+    dynamic_block(w, lit, dist, _lits(rng, 300, 0, 13) + [("L", 14), ("M", 3, 7), ("M", 3, 301), ("E",)],
+                  cl_seq=_rle(lit + dist, use_16=True), cl_lens=cl_lens)
+    b = _finish(out, "hclen_19_all_symbols", w.bytes())
+    assert b[0]["hclen"] == 19 and set(b[0]["cl_syms"]) == set(range(19))
+
+    # the largest header, behind a token round (its window starts inside the block)
+    b = _finish(out, "largest_header", _largest_header_block())
+    assert b[1]["header_bits"] == 17 + 3 * b[1]["hclen"] + 316 * 7 and len(b[0]["tokens"]) > RING and b[1]["at"] % 8
+
+    # zero runs across the HLIT / HDIST boundary
+    lit = [0] * 286
+    lit[0] = lit[256] = 1
+    dist = [0] * 29 + [1]
+    seq = [(1, 0), (18, 127), (18, 117 - 11), (1, 0), (18, 58 - 11), (1, 0)]
+    w = BitW()
+    dynamic_block(w, lit, dist, [("L", 0)] * 25 + [("E",)], cl_seq=seq)
+    b = _finish(out, "run_18_of_58_across_hlit_hdist", w.bytes())
+    assert b[0]["cl_syms"] == [1, 18, 18, 1, 18, 1] and b[0]["dist"] == dist
+    seq = [(1, 0), (18, 138 - 11), (18, 0), (18, 138 - 11), (18, 28 - 11)]  # 1 + 138 + 11 + 138 (150..287) + 28 = 316
+    w = BitW()
+    dynamic_block(w, lit, dist, [], cl_seq=seq)
+    w.put(0, 16)
+    bad("run_18_of_138_across_hlit_hdist", w.bytes(), 1, L.INFLATE_ENOEOB)
+
+    # stale tables: one BGZF block, dynamic blocks whose tables disagree on the same bit patterns
+    flat_lit, flat_dist = [8] * 226 + [9] * 60, [4] * 2 + [5] * 28
+    skew_lit = [0] * 258
+    for s, n in zip(list(range(65, 79)) + [256, 257], _skewed()):
+        skew_lit[s] = n
+    skew_dist = list(range(1, 10)) + [10, 11, 12, 13, 14, 15, 15]
+    few_lit = [0] * 258
+    for s in (70, 71, 256, 257):
+        few_lit[s] = 2
+
+    def flat_toks():
+        return _lits(rng, 120) + [("M", 20, 9), ("M", 258, 100)] + _lits(rng, 30)
+
+    def skew_toks():
+        t = _lits(rng, 150, 65, 79) + [("L", s) for s in range(65, 79)]
+        return t + [("X", 257, 0, ds, 0) for ds in range(16)]
+
+    def few_toks():
+        return _lits(rng, 90, 70, 72) + [("X", 257, 0, 0, 0)] * 3
+
+    w = BitW()
+    dynamic_block(w, flat_lit, flat_dist, flat_toks() + [("E",)], final=False)
+    dynamic_block(w, skew_lit, skew_dist, skew_toks() + [("E",)], cl_seq=_rle(skew_lit + skew_dist), final=False)
+    dynamic_block(w, few_lit, [1], few_toks() + [("E",)], cl_seq=_rle(few_lit + [1]), final=False)
+    dynamic_block(w, skew_lit, skew_dist, skew_toks() + [("E",)], cl_seq=_rle(skew_lit + skew_dist), final=False)
+    fixed_block(w, flat_toks() + [("E",)], final=False)
+    dynamic_block(w, few_lit, [1], few_toks() + [("E",)], cl_seq=_rle(few_lit + [1]), final=False)
+    dynamic_block(w, flat_lit, flat_dist, flat_toks() + [("E",)])
+    b = _finish(out, "stale_tables", w.bytes())
+    assert [x["type"] for x in b] == [2, 2, 2, 2, 1, 2, 2]
+    assert {t[4] for t in b[1]["tokens"]} == set(range(1, 16)) and {t[5] for t in b[1]["tokens"] if t[2]} == set(range(1, 16))
+    # ... and the one-bit distance code's unused bit behind the long distance codes
+    w = BitW()
+    dynamic_block(w, skew_lit, skew_dist, skew_toks() + [("E",)], cl_seq=_rle(skew_lit + skew_dist), final=False)
+    dynamic_block(w, few_lit, [1], few_toks(), cl_seq=_rle(few_lit + [1]))
+    w.code(canon(few_lit)[257], 2)
+    w.put(1, 1)
+    w.put(0, 32)
+    bad("stale_unused_distance_code", w.bytes(), 164 + 3 * 16 + 90 + 3 * 3 + 3, L.INFLATE_ECODE)
+
+    # the Z_SYNC_FLUSH shape: stored blocks (empty ones too) whose header starts at each bit 0..7
+    w = BitW()
+    at = []
+    for k in range(8):
+        nines = (k - w.nbits() - 2) % 8  # a fixed block of j 9-bit literals ends 10 + 9j + 8i bits on
+        fixed_block(w, _lits(rng, nines, 144, 256) + _lits(rng, 5, 0, 144) + [("E",)], final=False)
+        at.append(w.nbits() % 8)
+        stored_block(w, b"" if k % 2 else _bytes(rng, 10 + k), final=False)
+        dynamic_block(w, few_lit, [1], few_toks()[:11 + k] + [("E",)], cl_seq=_rle(few_lit + [1]), final=False)
+    stored_block(w, b"")
+    b = _finish(out, "stored_at_every_bit_offset", w.bytes())
+    assert at == list(range(8)) and [x["at"] % 8 for x in b if x["type"] == 0][:8] == at
+    assert [x["type"] for x in b] == [1, 0, 2] * 8 + [0]
+
+    w = BitW()
+    for k in range(300):
+        fixed_block(w, _lits(rng, 1) + [("E",)], final=k == 299)
+    b = _finish(out, "300_one_literal_fixed_blocks", w.bytes())
+    assert len(b) == 300 and all(len(x["tokens"]) == 1 for x in b)
+    return out
+
+
+DST_ISIZES = (1, 2, 15, 16, 17, 31, 33, 4097, 65535, 65536)
+SRC_CLENS = (1, 2, 3, 4, 5, 7)
+
+
+@functools.lru_cache(maxsize=None)
+def placements():
+    """(block, src % 4, dst % 16): the write-out's head / body / tail at every destination alignment
+    and the compressed window's first dword at every source alignment.  A block of clen 1 cannot be
+    valid (BFINAL + BTYPE + the 7-bit end-of-block code are 10 bits): it is the empty fixed block
+    cut to one byte, EINPUT, and what lies behind it in `comp` must not be read as its bits."""
+    out = []
+    text = _bamlike(65536, 3)
+    for n in DST_ISIZES:
+        comp = deflate(text[:n], 6)
+        assert ref(comp) == text[:n]
+        for a in range(16):
+            out.append((Block("isize_%d_dst_%d" % (n, a), comp, n, text[:n]), a % 4, a))
+    rng = _rng(12)
+    small = [Block("clen_1", b"\x03", 0, None, L.INFLATE_EINPUT), Block("clen_5_stored_empty", deflate(b"", 0), 0, b"")]
+    for clen, lits in ((2, 0), (3, 1), (4, 2), (5, 3), (7, 5)):
+        w = BitW()
+        fixed_block(w, _lits(rng, lits, 0, 144) + [("E",)])
+        assert len(w.bytes()) == clen
+        small.append(Block("clen_%d" % clen, w.bytes(), lits, ref(w.bytes())))
+    assert {len(b.comp) for b in small} == set(SRC_CLENS) and small[1].comp == b"\x01\x00\x00\xff\xff"
+    big = [Block("costliest_round", _costliest_block(), 65534, ref(_costliest_block())),
+           Block("largest_header", _largest_header_block(), len(ref(_largest_header_block())), ref(_largest_header_block()))]
+    for s in range(4):
+        for b in small + big:
+            out.append((Block("%s_src_%d" % (b.name, s), b.comp, b.isize, b.want, b.code), s, (5 * s + len(out)) % 16))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def flip_bases():
+    return [("dynamic", deflate(_bamlike(1000), 6)), ("fixed", deflate(_bamlike(300, 1), 6, zlib.Z_FIXED)),
+            ("stored", deflate(_bytes(_rng(13), 100), 0)), ("repeat_codes", _repeat_codes_block())]
+
+
+@functools.lru_cache(maxsize=None)
+def flips() -> List[Block]:
+    """every single-bit flip of four small streams, none left out.  zlib is the arbiter: a flipped
+    stream it inflates to exactly the claimed isize is a valid block with zlib's bytes; one it
+    rejects, or inflates to another size, is corrupt with code ANY (any nonzero status)."""
+    out: List[Block] = []
+    for name, comp in flip_bases():
+        isize, n = len(ref(comp)), [0, 0]
+        for bit in range(8 * len(comp)):
+            c = _flip(comp, bit)
+            try:
+                got = ref(c)
+            except zlib.error:
+                got = None
+            ok = got is not None and len(got) == isize
+            n[ok] += 1
+            out.append(Block("%s_bit_%d" % (name, bit), c, isize, got if ok else None, 0 if ok else ANY))
+        assert n[0] and n[1], (name, n)  # both classes are filled
+        assert n[0] + n[1] == 8 * len(comp)
     return out

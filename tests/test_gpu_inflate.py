@@ -20,8 +20,8 @@ pytestmark = pytest.mark.gpu
 class Device:
     """the launch's buffers on the GPU, kept between launches"""
 
-    def __init__(self, blocks):
-        comp, d, self.n_out = layout(blocks)
+    def __init__(self, blocks, lay=None):  # lay: a (comp, table, out size) other than layout()'s
+        comp, d, self.n_out = lay or layout(blocks)
         self.blocks, self.d, self.n_comp = blocks, d, len(comp)
         self.comp = torch.from_numpy(np.frombuffer(comp + b"\0", np.uint8).copy()).cuda()
         self.blk = torch.from_numpy(np.frombuffer(bytes(d), np.uint8).copy()).cuda()
