@@ -39,6 +39,10 @@ class InflateBlockC(C.Structure):  # bsdc_inflate_block
  INFLATE_ESHORT, INFLATE_EINPUT, INFLATE_ECOUNTS, INFLATE_ENOEOB, INFLATE_ECODE, INFLATE_ERANGE) = range(1, 14)
 
 
+# bsdc_image_rec as a numpy record: the gather's table (batch.FamilyBatch.gather)
+IMAGE_REC = [("src", "<i8"), ("l_seq", "<i4"), ("skip", "<i4"), ("len", "<i4"), ("slot", "<u4")]
+
+
 class FamilyBatchC(C.Structure):
     _fields_ = [("n_rec", C.c_int64), ("n_fam", C.c_int64),
                 ("fam_off", C.c_void_p), ("rec", C.c_void_p), ("rec_win", C.c_void_p),
@@ -67,7 +71,8 @@ EXPORTS = ("bsdc_abi_version", "bsdc_ctx_create", "bsdc_ctx_set_params", "bsdc_c
            "bsdc_model_tables_fp64", "bsdc_agree_tables", "bsdc_phred_buckets", "bsdc_bgzf_scratch_bytes",
            "bsdc_bgzf_deflate", "bsdc_bgzf_pack", "bsdc_host_register", "bsdc_host_unregister", "bsdc_filter",
            "bsdc_bgzf_inflate", "bsdc_bgzf_inflate_host", "bsdc_fastq_text_bound", "bsdc_fastq_tmp_bytes",
-           "bsdc_fastq_format", "bsdc_bgzf_crc32", "bsdc_bam_bytes_bound", "bsdc_bam_tmp_bytes", "bsdc_bam_format")
+           "bsdc_fastq_format", "bsdc_bgzf_crc32", "bsdc_bam_bytes_bound", "bsdc_bam_tmp_bytes", "bsdc_bam_format",
+           "bsdc_image_gather", "bsdc_image_gather_host", "bsdc_image_last_error")
 
 _lib = None
 
@@ -147,6 +152,13 @@ def load(path: str = LIB_PATH):
     lib.bsdc_bam_format.argtypes = [C.POINTER(ConsensusC), C.c_void_p, C.c_int32, C.c_int32, C.c_int64] + \
         [C.c_void_p] * 8 + [C.c_int64, C.c_void_p, C.c_void_p]
     lib.bsdc_bam_format.restype = C.c_int32
+    lib.bsdc_image_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bsdc_image_gather.restype = C.c_int32
+    lib.bsdc_image_gather_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                           C.c_void_p, C.c_void_p]
+    lib.bsdc_image_gather_host.restype = C.c_int32
+    lib.bsdc_image_last_error.restype = C.c_char_p
     if lib.bsdc_abi_version() != BSDC_ABI_VERSION:
         raise RuntimeError("libbsdc ABI %d != %d" % (lib.bsdc_abi_version(), BSDC_ABI_VERSION))
     if path == LIB_PATH:

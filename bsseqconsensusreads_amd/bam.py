@@ -32,7 +32,7 @@ from . import records as R
 
 IO_LIB_PATH = os.environ.get("BSDC_IO_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)),
                                                                  "libbsdc_io.so")
-BSDC_IO_ABI_VERSION = 15
+BSDC_IO_ABI_VERSION = 16
 _P = C.c_void_p
 # bsdc_inflate_fn (include/bsdc_io.h): user, comp, n_comp, blk, nblk, out, n_out -> 0 or an error
 INFLATE_FN = C.CFUNCTYPE(C.c_int32, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64)
@@ -48,7 +48,8 @@ class _Arrays(C.Structure):
     _fields_ = [(k, _P) for k in (
         "flag", "tid", "pos", "mapq", "l_seq", "seq_off", "seq", "qual", "cig_off", "n_cig", "cigar", "next_tid",
         "next_pos", "tlen", "name_id", "name_off", "name_buf", "mi_id", "mi_strand", "mi_off", "mi_buf", "mc_off",
-        "mc_n", "mc_cigar", "la", "rd", "aux_off", "aux", "header", "ref_len", "ref_name_off", "ref_name_buf")]
+        "mc_n", "mc_cigar", "la", "rd", "aux_off", "aux", "header", "ref_len", "ref_name_off", "ref_name_buf",
+        "raw_bases", "seq_src")]
 
 
 class _Records(C.Structure):
@@ -246,10 +247,13 @@ class BufferPool:
                 del self.free[min(range(len(self.free)), key=lambda i: self.free[i].size)]
 
 
-def _decode(lib, h, what: str, pool: Optional[BufferPool] = None):
+def _decode(lib, h, what: str, pool: Optional[BufferPool] = None, packed: bool = False, pin=None):
     """A bsdc_bam handle (whole file or stream chunk) -> (BamHeader, RawRecords, pooled buffer);
     frees nothing.  With `pool`, the record arrays are carved from one pooled buffer (bsdc_bam_copy
-    writes every element), returned for the caller to give back (else None)."""
+    writes every element), returned for the caller to give back (else None).  packed: no unpacked
+    bases (RawRecords.seq / qual None): the records' SEQ and QUAL fields as they lie in the file go
+    to RawRecords.raw_bases, at seq_src; pin(nbytes) -> uint8 array: where raw_bases goes (pinned
+    memory, which uploads asynchronously) instead of the pooled buffer."""
     s = _Sizes()
     lib.bsdc_bam_sizes_of(h, C.byref(s))
     n = s.n_rec
@@ -259,7 +263,8 @@ def _decode(lib, h, what: str, pool: Optional[BufferPool] = None):
         specs.append((max(int(k), 1), np.dtype(dt)))
         return len(specs) - 1
     A = dict(flag=z(n, np.uint16), tid=z(n, np.int32), pos=z(n, np.int32), mapq=z(n, np.uint8),
-             l_seq=z(n, np.int32), seq_off=z(n, np.int64), seq=z(s.n_bases, np.uint8), qual=z(s.n_bases, np.uint8),
+             l_seq=z(n, np.int32), seq_off=z(n, np.int64), seq=z(0 if packed else s.n_bases, np.uint8),
+             qual=z(0 if packed else s.n_bases, np.uint8),
              cig_off=z(n, np.int64), n_cig=z(n, np.int32), cigar=z(s.n_cigar, np.uint32),
              next_tid=z(n, np.int32), next_pos=z(n, np.int32), tlen=z(n, np.int32), name_id=z(n, np.int32),
              name_off=z(s.n_names + 1, np.int64), name_buf=z(s.name_bytes, np.uint8), mi_id=z(n, np.int32),
@@ -268,6 +273,11 @@ def _decode(lib, h, what: str, pool: Optional[BufferPool] = None):
              rd=z(n, np.int32), aux_off=z(n + 1, np.int64), aux=z(s.aux_bytes, np.uint8),
              header=z(s.header_bytes, np.uint8), ref_len=z(s.n_ref, np.int64),
              ref_name_off=z(s.n_ref + 1, np.int64), ref_name_buf=z(s.ref_name_bytes, np.uint8))
+    n_raw = int(s.n_bases + (s.n_bases + n) // 2 + 8)  # (bsdc_bam_arrays.raw_bases' bound, + slack)
+    if packed:
+        A["seq_src"] = z(n + 1, np.int64)
+        if pin is None:
+            A["raw_bases"] = z(n_raw, np.uint8)
     buf = None
     if pool is None:
         arrs = [np.zeros(k, dt) for k, dt in specs]
@@ -279,6 +289,8 @@ def _decode(lib, h, what: str, pool: Optional[BufferPool] = None):
             arrs.append(buf[o:o + k * dt.itemsize].view(dt))
             o += nb
     A = {key: arrs[i] for key, i in A.items()}
+    if packed and pin is not None:
+        A["raw_bases"] = pin(n_raw)
     a = _Arrays(**{k: _ptr(v) for k, v in A.items()})
     if lib.bsdc_bam_copy(h, C.byref(a)) != 0:
         raise OSError("%s: %s" % (what, lib.bsdc_io_last_error().decode()))
@@ -287,7 +299,8 @@ def _decode(lib, h, what: str, pool: Optional[BufferPool] = None):
                        [names_tab[i] for i in range(s.n_ref)], A["ref_len"][:s.n_ref].copy())
     raw = R.RawRecords(
         flag=A["flag"][:n], tid=A["tid"][:n], pos=A["pos"][:n], mapq=A["mapq"][:n], l_seq=A["l_seq"][:n],
-        seq_off=A["seq_off"][:n], seq=A["seq"][:s.n_bases], qual=A["qual"][:s.n_bases], cig_off=A["cig_off"][:n],
+        seq_off=A["seq_off"][:n], seq=None if packed else A["seq"][:s.n_bases],
+        qual=None if packed else A["qual"][:s.n_bases], cig_off=A["cig_off"][:n],
         n_cig=A["n_cig"][:n], cigar=A["cigar"][:s.n_cigar], next_tid=A["next_tid"][:n], next_pos=A["next_pos"][:n],
         tlen=A["tlen"][:n], name_id=A["name_id"][:n],
         names=StringTable(A["name_buf"][:s.name_bytes], A["name_off"][:s.n_names + 1]),
@@ -295,6 +308,9 @@ def _decode(lib, h, what: str, pool: Optional[BufferPool] = None):
         mi_names=StringTable(A["mi_buf"][:s.mi_bytes], A["mi_off"][:s.n_mi + 1], as_str=True),
         mc_off=A["mc_off"][:n], mc_n=A["mc_n"][:n], mc_cigar=A["mc_cigar"][:s.n_mc],
         aux=StringTable(A["aux"][:s.aux_bytes], A["aux_off"][:n + 1]), la_tag=A["la"][:n], rd_tag=A["rd"][:n])
+    if packed:
+        raw.seq_src = A["seq_src"][:n + 1]
+        raw.raw_bases = A["raw_bases"][:int(raw.seq_src[n])]
     return header, raw, buf
 
 
@@ -350,9 +366,10 @@ class StreamChunk:
         self.spill = b""       # spill entries (bsdc_bam_stream_spill) since the chunk before
         self.pool_buf = None   # decode(pool=...): the pooled buffer of the records, to give back
 
-    def decode(self, threads: int = 0, timing: Optional[dict] = None, pool: Optional[BufferPool] = None):
+    def decode(self, threads: int = 0, timing: Optional[dict] = None, pool: Optional[BufferPool] = None,
+               packed: bool = False, pin=None):
         """-> (BamHeader, RawRecords); `timing`: seconds added under "parse" (records, tags,
-        interning) and "copy" (the arrays copied out); `pool`: see _decode."""
+        interning) and "copy" (the arrays copied out); `pool`, `packed`, `pin`: see _decode."""
         import time
         lib, h = self._lib, self._h
         self._h = None
@@ -361,7 +378,7 @@ class StreamChunk:
             if lib.bsdc_bam_parse(h, int(threads)) != 0:
                 raise OSError("%s: %s" % (self._path, lib.bsdc_io_last_error().decode()))
             t1 = time.perf_counter()
-            *out, self.pool_buf = _decode(lib, h, self._path, pool)
+            *out, self.pool_buf = _decode(lib, h, self._path, pool, packed, pin)
             if self.keys:  # the records' coarse TemplateCoordinate keys (splicing deferred families)
                 kk = np.zeros(2 * max(out[1].n, 1), np.int64)
                 if lib.bsdc_bam_rec_keys(h, _ptr(kk)) != 0:

@@ -140,6 +140,10 @@ class FamilyBatch:
     split_part_recs: np.ndarray = field(default_factory=lambda: np.zeros((0, 4), np.uint32))  # u32 [PR, 4]
     split_fams: np.ndarray = field(default_factory=lambda: np.zeros((0, 8), np.uint32))   # u32 [S, 8], arena offsets relative
     split_part_arena: int = 16
+    # ---- images made on the device (materialize(gather=True)): seq and qual are None and `gather`
+    # is the bsdc_image_rec table ([R], _lib.IMAGE_REC) Engine.image makes them from, its slot
+    # column = rec_off (after split_hbm_bucket) ----
+    gather: Optional[np.ndarray] = None
 
     @property
     def n_rec(self) -> int:
@@ -182,6 +186,8 @@ class FamilyBatch:
         d = {"fam_off": self.fam_off, "rec": np.ascontiguousarray(rec, dtype=np.uint32),
              "rec_win": np.ascontiguousarray(self.rec_win, dtype=np.uint32)}
         for k in ("cig_off", "cig_info", "cigar", "rt", "seq", "qual", "large_fams"):
+            if self.gather is not None and k in ("seq", "qual"):
+                continue  # (the images are made in HBM: Engine.image)
             d[k] = getattr(self, k)
         d["small_fams"] = np.ascontiguousarray(self.fam_entry[self.small_fams.astype(np.int64)]).reshape(-1) \
             if self.small_fams.shape[0] else np.zeros(4, np.uint32)
@@ -350,8 +356,15 @@ def predict_rd(raw: R.RawRecords, ref: R.Reference, sel: np.ndarray, sL: np.ndar
         nib = np.where(idx & 1, b & 0xF, b >> 4)
         return np.where(ok, nib, 15)
 
-    lastpos = raw.seq_off[sel] + sL[sel] + Ls - 1
-    last = np.where(Ls > 0, raw.seq[np.clip(lastpos, 0, max(raw.seq.shape[0] - 1, 0))], refnib(np.zeros_like(Ls)))
+    if raw.seq is None:  # records without unpacked bases: the nibble of the packed SEQ field
+        j = np.maximum(sL[sel].astype(np.int64) + Ls - 1, 0)
+        at = np.clip(raw.seq_src[sel] + (j >> 1), 0, max(raw.raw_bases.shape[0] - 1, 0))
+        b = raw.raw_bases[at] if raw.raw_bases.shape[0] else np.zeros_like(j)
+        lastb = np.where(j & 1, b & 15, b >> 4)
+    else:
+        lastpos = raw.seq_off[sel] + sL[sel] + Ls - 1
+        lastb = raw.seq[np.clip(lastpos, 0, max(raw.seq.shape[0] - 1, 0))]
+    last = np.where(Ls > 0, lastb, refnib(np.zeros_like(Ls)))
     return (last == 2) & (refnib(Lp - 1) == 2) & (refnib(Lp) == 4)
 
 
@@ -675,16 +688,19 @@ def route_small_cap(plan: FamilyPlan, f0: int, f1: int, cap: int = SMALL_ARENA_C
     return mid if 2 * int(sizes[small & (need > mid)].sum()) > int(sizes[small].sum()) else cap
 
 
-def materialize(plan: FamilyPlan, f0: int, f1: int, small_cap: Optional[int] = None, images=None) -> FamilyBatch:
+def materialize(plan: FamilyPlan, f0: int, f1: int, small_cap: Optional[int] = None, images=None,
+                gather: bool = False) -> FamilyBatch:
     """The device batch of plan families [f0, f1) (family ids renumbered from 0): C++ (hostplan)
     for the step-5 modes, materialize_py otherwise; then the HBM bucket's families cut into parts
     (split_hbm_bucket).  small_cap: the largest small-family arena (None: route_small_cap).
-    images: see hostplan.materialize."""
+    images, gather: see hostplan.materialize (gather: the C++ path only)."""
     from . import hostplan
     if small_cap is None:
         small_cap = route_small_cap(plan, f0, f1)
+    if gather and not (plan.mode in ("full", "vote") and hostplan.enabled()):
+        raise ValueError("materialize(gather=True): step-5 modes with the native host plan only")
     if plan.mode in ("full", "vote") and hostplan.enabled():
-        return split_hbm_bucket(hostplan.materialize(plan, f0, f1, small_cap, images=images))
+        return split_hbm_bucket(hostplan.materialize(plan, f0, f1, small_cap, images=images, gather=gather))
     return split_hbm_bucket(materialize_py(plan, f0, f1, small_cap))
 
 
@@ -741,9 +757,15 @@ def split_hbm_bucket(fb: FamilyBatch, part_cap: Optional[int] = None, threads: i
     fb.split_part_arena = cap
     # each cut family's image re-laid out part after part (contiguous parts stage in 16-B chunks)
     assert fb.rec_off.dtype == np.uint32 and fb.rec_off.flags.c_contiguous
-    assert fb.seq.flags.c_contiguous and fb.qual.flags.c_contiguous
-    lib.bsdc_split_move(fb.seq.ctypes.data, fb.qual.ctypes.data, fb.rec_off.ctypes.data, fb.split_fams.ctypes.data,
-                        int(fb.split_fams.shape[0]), parts.ctypes.data, part_recs.ctypes.data, int(threads))
+    if fb.gather is not None:  # the images are gathered on the device, at the slots as they are after the cut
+        lib.bsdc_split_move(None, None, fb.rec_off.ctypes.data, fb.split_fams.ctypes.data,
+                            int(fb.split_fams.shape[0]), parts.ctypes.data, part_recs.ctypes.data, int(threads))
+        fb.gather["slot"] = fb.rec_off
+    else:
+        assert fb.seq.flags.c_contiguous and fb.qual.flags.c_contiguous
+        lib.bsdc_split_move(fb.seq.ctypes.data, fb.qual.ctypes.data, fb.rec_off.ctypes.data,
+                            fb.split_fams.ctypes.data, int(fb.split_fams.shape[0]), parts.ctypes.data,
+                            part_recs.ctypes.data, int(threads))
     keep = ~cut
     tail, o = [], 0
     for k in sizes:  # the families left whole stay in their buckets

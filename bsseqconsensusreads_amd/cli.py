@@ -64,6 +64,10 @@ def parse(argv):
                        help="write, checksum and deflate the output BAM's records (consensus tags included) on the "
                             "GPU (streaming, --gpus 1; needs OUT.bam; implies the GPU deflate for the BAM; the file "
                             "of a --gpu-bgzf run)")
+        p.add_argument("--gpu-image", default="false", choices=("true", "false"),
+                       help="make the family images on the GPU from the records' SEQ / QUAL bytes instead of "
+                            "unpacking and copying every base on the host (streaming, --gpus 1; the same output "
+                            "files)")
         p.add_argument("--batch-bases", type=int, default=None, help="device batch budget in bases")
         p.add_argument("--chunk-mb", type=int, default=64, help="--stream: record MiB per chunk")
         if name == "step5":
@@ -129,6 +133,11 @@ def parse(argv):
             ap.error("--gpu-bam is not supported with --gpus %d yet (one process, one GPU)" % a.gpus)
         if a.stream == "false":
             ap.error("--gpu-bam applies to the streaming step only: not with --stream false")
+    if a.gpu_image == "true":
+        if getattr(a, "gpus", 1) > 1:
+            ap.error("--gpu-image is not supported with --gpus %d yet (one process, one GPU)" % a.gpus)
+        if a.stream == "false":
+            ap.error("--gpu-image applies to the streaming step only: not with --stream false")
     if a.gpu_inflate == "true" and a.stream == "false":
         print("warning: --gpu-inflate applies to the streaming step only; --stream false inflates on the host",
               file=sys.stderr)
@@ -230,7 +239,10 @@ def main(argv=None) -> int:
                                         fq, tags=a.output_per_base_tags == "true", chunk_bytes=a.chunk_mb << 20,
                                         batch_bases=a.batch_bases, gpu_bgzf=a.gpu_bgzf == "true", filter=flt,
                                         gpu_inflate=a.gpu_inflate == "true", gpu_fastq=a.gpu_fastq == "true",
-                                        gpu_bam=a.gpu_bam == "true")
+                                        gpu_bam=a.gpu_bam == "true", gpu_image=a.gpu_image == "true")
+            elif a.cmd == "step5" and a.gpu_image == "true":
+                raise ValueError("--gpu-image applies to the streaming step only: %s is not coordinate-sorted "
+                                 "and would be read whole" % a.input)
             elif a.cmd == "step5" and a.gpu_bam == "true":
                 raise ValueError("--gpu-bam applies to the streaming step only: %s is not coordinate-sorted "
                                  "and would be read whole" % a.input)
@@ -247,7 +259,7 @@ def main(argv=None) -> int:
                                             batch_bases=a.batch_bases, gpu_bgzf=a.gpu_bgzf == "true",
                                             min_consensus_base_quality=a.min_consensus_base_quality, filter=flt,
                                             gpu_inflate=a.gpu_inflate == "true", gpu_fastq=a.gpu_fastq == "true",
-                                            gpu_bam=a.gpu_bam == "true")
+                                            gpu_bam=a.gpu_bam == "true", gpu_image=a.gpu_image == "true")
             else:
                 info = bam.molecular(a.input, out, eng, a.read_name_prefix, a.threads, a.compression, fq,
                                      tags=a.output_per_base_tags == "true",

@@ -91,6 +91,14 @@ inline uint32_t ref_nib(const bsdc_host_reference *ref, int64_t i) {
     return (i & 1) ? (b & 0xFu) : (b >> 4);
 }
 
+// base j of record k: the unpacked code, or (records without unpacked bases) the nibble of its
+// SEQ field as the BAM packs it, high nibble first
+inline uint32_t rec_base(const bsdc_host_records *R, int64_t k, int64_t j) {
+    if (R->seq) return R->seq[R->seq_off[k] + j];
+    const uint8_t b = R->raw_bases[R->seq_src[k] + (j >> 1)];
+    return (j & 1) ? (b & 0xFu) : (b >> 4);
+}
+
 struct PlanOut {
     std::vector<int64_t> order, fam_off, t2_rank, partner_raw, sL, L, kfirst, kn;
     std::vector<int32_t> fam_mi;
@@ -295,7 +303,7 @@ int32_t bsdc_plan_families(const bsdc_host_records *R, const bsdc_host_reference
                     const int64_t Ls = P.L[k], Lp = Ls + 1;
                     const int64_t avail = coff >= 0 ? std::min(std::max<int64_t>(clen - np0, 0), Lp + 1) : 0;
                     auto refnib = [&](int64_t j) -> uint32_t { return j < avail ? ref_nib(ref, coff + np0 + j) : 15u; };
-                    const uint32_t last = Ls > 0 ? R->seq[R->seq_off[k] + P.sL[k] + Ls - 1] : refnib(0);
+                    const uint32_t last = Ls > 0 ? rec_base(R, k, P.sL[k] + Ls - 1) : refnib(0);
                     rdp = last == 2 && refnib(Lp - 1) == 2 && refnib(Lp) == 4;
                 }
                 const bool er = P.ext_right[k], el = P.ext_left[k];
@@ -529,6 +537,9 @@ int32_t bsdc_materialize_fill(bsdc_batch *b, const bsdc_batch_arrays *o, int64_t
     const int64_t nr = b->r1 - b->r0, nf = b->f1 - b->f0;
     const bool full = b->mode_full != 0;
     const int32_t max_len = b->max_len;
+    const bool images = o->seq && o->qual;  // (else the images are gathered on the device: image_rec)
+    if (!images && (o->seq || o->qual)) return fail(BSDC_EINVAL, "materialize: seq and qual go together");
+    if (images && !R->seq) return fail(BSDC_EINVAL, "materialize: records without unpacked bases make no host images");
     // ---- per record: cigars (complex = any kept op not M/=/X), image copy, words ----
     std::vector<int64_t> nops(nr), reflen(nr);
     std::vector<uint8_t> cplx(nr);
@@ -554,6 +565,15 @@ int32_t bsdc_materialize_fill(bsdc_batch *b, const bsdc_batch_arrays *o, int64_t
         // to the next record's slot (or the image end) is written here, the tools' room and the
         // family alignment as zeros, so the images need no zeroed (fresh) memory
         const int64_t L = pv.L[k], so = R->seq_off[k] + pv.sL[k], S = b->rec_off[i], d = S + 1;
+        if (o->image_rec) {  // the device gather's table entry (bsdc_image_gather)
+            bsdc_image_rec &g = o->image_rec[i];
+            g.src = R->seq_src ? R->seq_src[k] : 0;
+            g.l_seq = R->l_seq[k];
+            g.skip = (int32_t)pv.sL[k];
+            g.len = (int32_t)L;
+            g.slot = (uint32_t)S;
+        }
+        if (!images) continue;
         const int64_t end = i + 1 < nr ? b->rec_off[i + 1] : b->n_slots;
         o->qual[S] = 0;
         std::memcpy(o->qual + d, R->qual + so, (size_t)L);
@@ -568,7 +588,8 @@ int32_t bsdc_materialize_fill(bsdc_batch *b, const bsdc_batch_arrays *o, int64_t
         if (j < L) *p++ = (uint8_t)((s[j] & 15) << 4);  // a high nibble, then zeros
         std::memset(p, 0, (size_t)(o->seq + (end >> 1) - p));
     }
-    if (nr == 0) {
+    if (!images) {
+    } else if (nr == 0) {
         std::memset(o->qual, 0, (size_t)b->n_slots);
         std::memset(o->seq, 0, (size_t)(b->n_slots >> 1));
     } else if (b->rec_off[0] > 0) {  // (leading empty families)
@@ -935,6 +956,16 @@ void bsdc_split_move(uint8_t *seq, uint8_t *qual, uint32_t *rec_off, const uint3
         const uint32_t *sf = split_fams + 8 * f;
         const uint32_t r0 = sf[1], img = sf[3], p0 = sf[4], np = sf[5];
         const uint32_t base = rec_off[r0];
+        if (!seq || !qual) {  // (the images come from the device gather: only the slots move)
+            for (uint32_t p = p0; p < p0 + np; p++) {
+                const uint32_t *pt = parts + 4 * (int64_t)p;
+                for (uint32_t q = 0; q < (pt[2] & 0xFFu); q++) {
+                    const uint32_t *w = part_recs + 4 * ((int64_t)pt[1] + q);
+                    rec_off[w[0]] = w[3];
+                }
+            }
+            continue;
+        }
         std::vector<uint8_t> tq(img), ts(img / 2 + 1);
         std::memcpy(tq.data(), qual + base, img);  // (entries no record holds keep their bytes)
         std::memcpy(ts.data(), seq + base / 2, img / 2);

@@ -2099,7 +2099,7 @@ int32_t bsdc_bam_copy(const bsdc_bam *b, const bsdc_bam_arrays *a) {
     const int64_t nr = (int64_t)b->rec_start.size();
     const uint8_t *d = b->data.data();
     // running offsets (sequential prefix sums)
-    std::vector<int64_t> so(nr + 1), co(nr + 1), ao(nr + 1), mo(nr + 1);
+    std::vector<int64_t> so(nr + 1), co(nr + 1), ao(nr + 1), mo(nr + 1), ro(nr + 1);
     for (int64_t k = 0; k < nr; k++) {
         const uint8_t *r = d + b->rec_start[k];
         const int64_t bs = rd32(r);
@@ -2108,6 +2108,7 @@ int32_t bsdc_bam_copy(const bsdc_bam *b, const bsdc_bam_arrays *a) {
         const int32_t l_seq = rdi32(r + 20);
         const int64_t auxlen = 4 + bs - (36 + l_name + 4 * n_cig + (l_seq + 1) / 2 + l_seq);
         so[k + 1] = so[k] + l_seq;
+        ro[k + 1] = ro[k] + (l_seq + 1) / 2 + l_seq;
         co[k + 1] = co[k] + n_cig;
         ao[k + 1] = ao[k] + auxlen;
         mo[k + 1] = mo[k] + b->mc_n[k];
@@ -2133,10 +2134,15 @@ int32_t bsdc_bam_copy(const bsdc_bam *b, const bsdc_bam_arrays *a) {
         const uint8_t *c = r + 36 + l_name;
         for (int i = 0; i < n_cig; i++) a->cigar[co[k] + i] = rd32(c + 4 * i);
         const uint8_t *sq = c + 4 * n_cig;
-        uint8_t *dst = a->seq + so[k];
-        for (int32_t i = 0; i < l_seq >> 1; i++) memcpy(dst + 2 * i, &kNibblePairs.v[sq[i]], 2);
-        if (l_seq & 1) dst[l_seq - 1] = (uint8_t)(sq[l_seq >> 1] >> 4);
-        memcpy(a->qual + so[k], sq + (l_seq + 1) / 2, (size_t)l_seq);
+        if (a->raw_bases) {  // SEQ and QUAL as they lie in the record (they are adjacent): one copy
+            memcpy(a->raw_bases + ro[k], sq, (size_t)(ro[k + 1] - ro[k]));
+            a->seq_src[k] = ro[k];
+        } else {
+            uint8_t *dst = a->seq + so[k];
+            for (int32_t i = 0; i < l_seq >> 1; i++) memcpy(dst + 2 * i, &kNibblePairs.v[sq[i]], 2);
+            if (l_seq & 1) dst[l_seq - 1] = (uint8_t)(sq[l_seq >> 1] >> 4);
+            memcpy(a->qual + so[k], sq + (l_seq + 1) / 2, (size_t)l_seq);
+        }
         const uint8_t *aux = sq + (l_seq + 1) / 2 + l_seq;
         memcpy(a->aux + ao[k], aux, (size_t)(ao[k + 1] - ao[k]));
         a->aux_off[k] = ao[k];
@@ -2164,6 +2170,7 @@ int32_t bsdc_bam_copy(const bsdc_bam *b, const bsdc_bam_arrays *a) {
         (void)bs;
     }
     a->aux_off[nr] = ao[nr];
+    if (a->raw_bases) a->seq_src[nr] = ro[nr];
     int64_t o = 0;
     for (size_t i = 0; i < b->names.size(); i++) {
         a->name_off[i] = o;

@@ -101,6 +101,14 @@ class DeviceBatch:
             self.t[k] = h.to(device, non_blocking=h.is_pinned())
         F, Rn = fb.n_fam, fb.n_rec
         self.stride = fb.stride
+        self.gather_host = None
+        if fb.gather is not None:  # the images are made here in HBM (Engine.image), every byte of them
+            self.t["seq"] = torch.empty(fb.n_slots // 2 + 64, dtype=torch.uint8, device=device)
+            self.t["qual"] = torch.empty(fb.n_slots + 64, dtype=torch.uint8, device=device)
+            self.gather_host = np.ascontiguousarray(fb.gather)  # (the launcher checks this copy)
+            self.t["gather"] = torch.from_numpy(self.gather_host.view(np.uint8) if fb.n_rec else
+                                                np.zeros(8, np.uint8)).to(device, non_blocking=True)
+        self.n_slots = fb.n_slots
         self.status = torch.zeros(max(F, 1), dtype=torch.uint8, device=device)
         self.len = torch.zeros(max(2 * F, 1), dtype=torch.int16, device=device)
         self.seq = torch.zeros(max(F * self.stride, 16), dtype=torch.uint8, device=device)
@@ -405,10 +413,40 @@ class Engine:
         self._check(rc, "bsdc_load_reference")
         self.ref = ref
 
-    def upload(self, fb: FamilyBatch, dump: bool = False, tags: bool = False, filt: bool = False) -> DeviceBatch:
-        """filt: also the outputs of `filter` (which reads the tags' rows: tags is then on)."""
+    def upload(self, fb: FamilyBatch, dump: bool = False, tags: bool = False, filt: bool = False,
+               raw_dev: Optional[torch.Tensor] = None) -> DeviceBatch:
+        """filt: also the outputs of `filter` (which reads the tags' rows: tags is then on).  A batch
+        without host images (fb.gather) needs raw_dev, its records' SEQ / QUAL bytes in HBM
+        (upload_raw), and gets its images made there (image) on the current stream."""
         with torch.cuda.device(self.device):
-            return DeviceBatch(fb, self.device, dump, tags or filt, filt)
+            db = DeviceBatch(fb, self.device, dump, tags or filt, filt)
+            if fb.gather is not None:
+                if raw_dev is None:
+                    raise ValueError("a batch without host images (FamilyBatch.gather) needs raw_dev (upload_raw)")
+                self.image(db, raw_dev)
+            return db
+
+    def upload_raw(self, raw_bases: np.ndarray) -> torch.Tensor:
+        """A chunk's records' SEQ / QUAL bytes (RawRecords.raw_bases) into HBM on the current stream,
+        asynchronously from pinned memory: what `image` reads for each of the chunk's batches.  The
+        tensor is allocated and used on one stream; dropping it after the last batch's launch frees
+        it in stream order (torch's caching allocator)."""
+        a = np.ascontiguousarray(raw_bases, np.uint8)
+        h = torch.from_numpy(a if a.shape[0] else np.zeros(4, np.uint8))
+        with torch.cuda.device(self.device):
+            return h.to(self.device, non_blocking=h.is_pinned())
+
+    def image(self, db: DeviceBatch, raw_dev: torch.Tensor, stream: Optional[torch.cuda.Stream] = None):
+        """The batch's family images made in HBM from the records' bytes (bsdc_image_gather), enqueued
+        on the stream the vote runs on, before it."""
+        if db.gather_host is None:
+            raise ValueError("the batch has host images (no FamilyBatch.gather)")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        rc = self.lib.bsdc_image_gather(self.ctx, C.c_void_p(_dptr(raw_dev)), int(raw_dev.numel()),
+                                        C.c_void_p(_dptr(db.t["gather"])), C.c_void_p(db.gather_host.ctypes.data),
+                                        db.n_rec, db.n_slots, C.c_void_p(_dptr(db.t["seq"])),
+                                        C.c_void_p(_dptr(db.t["qual"])), C.c_void_p(s.cuda_stream))
+        self._check(rc, "bsdc_image_gather")
 
     def run(self, db: DeviceBatch, mode: int, stream: Optional[torch.cuda.Stream] = None):
         s = stream if stream is not None else torch.cuda.current_stream(self.device)

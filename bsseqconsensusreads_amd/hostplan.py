@@ -24,7 +24,8 @@ SMALL_BUCKETS_N, LARGE_BUCKETS_N = 8, 6  # BSDC_SMALL_BUCKETS, BSDC_LARGE_BUCKET
 class _Records(C.Structure):
     _fields_ = [("n", C.c_int64)] + [(k, _P) for k in (
         "flag", "tid", "pos", "l_seq", "seq_off", "seq", "qual", "cig_off", "n_cig", "cigar", "next_tid", "next_pos",
-        "tlen", "name_id", "mi_id", "mi_strand", "mc_off", "mc_n", "mc_cigar", "mi_rank", "name_rank")]
+        "tlen", "name_id", "mi_id", "mi_strand", "mc_off", "mc_n", "mc_cigar", "mi_rank", "name_rank", "raw_bases",
+        "seq_src")]
 
 
 class _Reference(C.Structure):
@@ -48,7 +49,7 @@ class _BatchSizes(C.Structure):
 
 class _BatchArrays(C.Structure):
     _fields_ = [(k, _P) for k in ("seq", "qual", "rec", "rec_win", "rt", "cig_off", "cig_info", "cigar", "src",
-                                  "fam_off", "fam_entry", "need_l", "img", "cls", "large_caps")]
+                                  "fam_off", "fam_entry", "need_l", "img", "cls", "large_caps", "image_rec")]
 
 
 _lib = None
@@ -119,9 +120,14 @@ class _RecordsView:
                       ("name_id", np.int32), ("mi_id", np.int32), ("mi_strand", np.int8), ("mc_off", np.int64),
                       ("mc_n", np.int32), ("mc_cigar", np.uint32)):
             a = getattr(raw, f)
+            if a is None:  # records without unpacked bases: seq and qual stay NULL (raw_bases below)
+                continue
             if a.shape[0] == 0:  # a valid pointer for empty stores
                 a = np.zeros(1, dt)
             setattr(s, f, k(a, dt))
+        if raw.seq is None:
+            s.raw_bases = k(raw.raw_bases if raw.raw_bases.shape[0] else np.zeros(1, np.uint8), np.uint8)
+            s.seq_src = k(raw.seq_src if raw.seq_src.shape[0] else np.zeros(1, np.int64), np.int64)
         if with_ranks and raw.n:
             s.mi_rank = k(lex_rank(raw.mi_names, np.maximum(raw.mi_id, 0)), np.int64)
             s.name_rank = k(lex_rank(raw.names, raw.name_id), np.int64)
@@ -183,15 +189,22 @@ def plan_families(raw: R.RawRecords, mode: str = "full", ref: Optional[R.Referen
     return FamilyPlan(raw=raw, mode=mode, ref=ref, **out)
 
 
-def materialize(plan, f0: int, f1: int, small_cap: int, n_threads: int = 0, images=None):
+def materialize(plan, f0: int, f1: int, small_cap: int, n_threads: int = 0, images=None, gather: bool = False):
     """batch.materialize in C++ (plans of modes 'full' / 'vote').  images(n_slots) -> (seq, qual):
     caller-owned uint8 arrays of at least n_slots / 2 and n_slots bytes for the family images
-    (e.g. pinned staging buffers, Engine.stage_images); the fill writes every byte of them."""
+    (e.g. pinned staging buffers, Engine.stage_images); the fill writes every byte of them.
+    gather: no images (FamilyBatch.seq / qual None) but the table the device makes them from
+    (FamilyBatch.gather, bsdc_image_gather; its src column points into plan.raw.raw_bases, so the
+    records are ones decoded without unpacked bases, records.pack_bases' form)."""
     from . import batch as B
     if plan.mode not in ("full", "vote"):
         raise ValueError("native materialize: mode 'full' or 'vote', not %r" % plan.mode)
     lib = _load()
     raw = plan.raw
+    if gather and raw.raw_bases is None:
+        raise ValueError("materialize(gather=True) needs records without unpacked bases (raw_bases / seq_src)")
+    if not gather and raw.seq is None:
+        raise ValueError("records without unpacked bases make no host images: materialize(gather=True)")
     rv = _RecordsView(raw, with_ranks=False)
     keep = []
     rs = _ref_struct(plan.ref, keep)
@@ -214,7 +227,12 @@ def materialize(plan, f0: int, f1: int, small_cap: int, n_threads: int = 0, imag
         raise ValueError(_err(lib))
     try:
         nr, nf, n_slots = sz.n_rec, sz.n_fam, sz.n_slots
-        if images is not None:
+        table = None
+        if gather:
+            from ._lib import IMAGE_REC
+            seq_img = qual_img = None
+            table = np.empty(max(nr, 1), np.dtype(IMAGE_REC))
+        elif images is not None:
             seq_img, qual_img = images(n_slots)
             seq_img, qual_img = seq_img[:n_slots // 2], qual_img[:n_slots]
         else:
@@ -226,7 +244,7 @@ def materialize(plan, f0: int, f1: int, small_cap: int, n_threads: int = 0, imag
                  fam_off=np.empty(nf + 1, np.uint32), fam_entry=np.empty((nf, 4), np.uint32),
                  need_l=np.empty(nf, np.int64), img=np.empty(nf, np.int64), cls=np.empty(nf, np.int8))
         caps = np.asarray(B.LARGE_BUCKETS, np.int64)
-        ba = _BatchArrays(large_caps=_p(caps), **{k: _p(v) for k, v in a.items()})
+        ba = _BatchArrays(large_caps=_p(caps), image_rec=_p(table), **{k: _p(v) for k, v in a.items()})
         nc = C.c_int64()
         rc = lib.bsdc_materialize_fill(h, C.byref(ba), C.byref(nc))
         if rc != 0:
@@ -274,7 +292,8 @@ def materialize(plan, f0: int, f1: int, small_cap: int, n_threads: int = 0, imag
         cigar=a["cigar"][:nc] if nc else np.zeros(1, np.uint32), rt=a["rt"], seq=a["seq"], qual=a["qual"],
         small_buckets=buckets, small_arenas=arenas, large_buckets=lbuckets, large_arenas=larenas,
         max_len=int(sz.max_len), src=order, fam_mi=plan.fam_mi[f0:f1].astype(np.int32), n_bases=int(sz.n_bases),
-        n_slots=int(n_slots), t2_rank=plan.t2_rank[r0:r1], split_ext=bool(plan.fam_split[f0:f1].any()))
+        n_slots=int(n_slots), t2_rank=plan.t2_rank[r0:r1], split_ext=bool(plan.fam_split[f0:f1].any()),
+        gather=None if table is None else table[:nr])
 
 
 def enabled() -> bool:

@@ -317,16 +317,18 @@ def run_ranges(engine: Engine, plan: FamilyPlan, ranges, mode: int, tags: bool =
     return run_batches(engine, staged(), mode, tags, T, filter, molecular)
 
 
-def materialize_ranges(plan: FamilyPlan, ranges, images=None) -> List[FamilyBatch]:
+def materialize_ranges(plan: FamilyPlan, ranges, images=None, gather: bool = False) -> List[FamilyBatch]:
     """The device batches of plan family ranges (batch.materialize each), for run_batches; `images`
-    e.g. a PinnedPool's, so that they upload asynchronously."""
-    return [materialize(plan, a, b, images=images) for a, b in ranges]
+    e.g. a PinnedPool's, so that they upload asynchronously; gather: no host images, the device
+    makes them (run_batches' raw_bases)."""
+    kw = {"gather": True} if gather else {}
+    return [materialize(plan, a, b, images=images, **kw) for a, b in ranges]
 
 
 def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
                 timing: Optional[dict] = None, filter: Optional[FilterParams] = None,
                 molecular: bool = False, fastq_names=None, seqqual: bool = True, bam_tables=None,
-                bam_tags: bool = True) -> List[Consensus]:
+                bam_tags: bool = True, raw_bases: Optional[np.ndarray] = None) -> List[Consensus]:
     """Materialized batches (any iterable, taken one at a time) through the kernels, one launch
     each, output per batch in order; a batch uploads and launches before the one before it is
     fetched.  `timing`: seconds added per host step (upload, fetch = wait + copy out, unpack).
@@ -338,11 +340,15 @@ def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
     `bam_tables` (batch -> its families' read names and aux bytes, two packed tables): each batch's
     BAM records are written on the device after its vote or filter (Engine.bam_records; bam_tags:
     with the consensus tags, whose rows the vote then leaves there) and its Consensus carries the
-    handle (Consensus.bamrec); the ss rows are not fetched."""
+    handle (Consensus.bamrec); the ss rows are not fetched.
+    `raw_bases` (RawRecords.raw_bases of the batches' records): batches without host images
+    (materialize(gather=True)) get theirs made in HBM from it (Engine.image); it goes up once, with
+    the first batch, and is released behind the last batch's launch."""
     import time
     T = timing if timing is not None else {}
     parts: List[Consensus] = []
     prev = None
+    raw_dev = None
 
     def out(fb, db):
         t0 = time.perf_counter()
@@ -360,7 +366,12 @@ def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
         T["unpack"] = T.get("unpack", 0.0) + time.perf_counter() - t1
     for fb in batches:
         t0 = time.perf_counter()
-        db = engine.upload(fb, tags=tags or (bam_tables is not None and bam_tags), filt=filter is not None)
+        if fb.gather is not None and raw_dev is None:
+            if raw_bases is None:
+                raise ValueError("batches without host images need raw_bases (the records' SEQ / QUAL bytes)")
+            raw_dev = engine.upload_raw(raw_bases)
+        db = engine.upload(fb, tags=tags or (bam_tables is not None and bam_tags), filt=filter is not None,
+                           raw_dev=raw_dev)
         engine.run(db, mode | (MODE_TAGS if db.tags else 0))
         if filter is not None:
             engine.filter(db, filter, molecular)
@@ -372,6 +383,7 @@ def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
         if prev is not None:
             out(*prev)
         prev = (fb, db)
+    del raw_dev  # (freed in stream order, behind the last gather)
     if prev is not None:
         out(*prev)
     return parts

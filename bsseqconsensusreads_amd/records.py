@@ -146,16 +146,29 @@ class RawRecords:
     aux: Optional[List[bytes]] = None  # raw aux bytes per record (None for synthetic data)
     la_tag: Optional[np.ndarray] = None  # i32 LA / RD tags when present (-1 absent), for tool-2-only input
     rd_tag: Optional[np.ndarray] = None
+    # records decoded without unpacked bases (bam.StreamChunk.decode(packed=True)): seq and qual are
+    # None; raw_bases holds every record's SEQ field ((l_seq + 1) / 2 bytes, two codes a byte, high
+    # nibble first, as in the BAM) followed by its QUAL field, record k's SEQ at seq_src[k]
+    raw_bases: Optional[np.ndarray] = None  # u8
+    seq_src: Optional[np.ndarray] = None    # i64
 
     @property
     def n(self) -> int:
         return int(self.flag.shape[0])
 
     def record_seq(self, k: int) -> np.ndarray:
+        if self.seq is None:
+            s, l = int(self.seq_src[k]), int(self.l_seq[k])
+            b = self.raw_bases[s:s + (l + 1) // 2]
+            return np.stack([b >> 4, b & 15], axis=1).reshape(-1)[:l]
         o = int(self.seq_off[k])
         return self.seq[o:o + int(self.l_seq[k])]
 
     def record_qual(self, k: int) -> np.ndarray:
+        if self.qual is None:
+            l = int(self.l_seq[k])
+            s = int(self.seq_src[k]) + (l + 1) // 2
+            return self.raw_bases[s:s + l]
         o = int(self.seq_off[k])
         return self.qual[o:o + int(self.l_seq[k])]
 
@@ -294,6 +307,47 @@ def take(raw: RawRecords, idx: np.ndarray) -> RawRecords:
         mc_off=np.where(has_mc, mo, -1), mc_n=raw.mc_n[idx], mc_cigar=raw.mc_cigar[mi_],
         aux=None if raw.aux is None else [raw.aux[int(k)] for k in idx], la_tag=sub(raw.la_tag),
         rd_tag=sub(raw.rd_tag))
+
+
+def unpack_bases(raw: RawRecords) -> RawRecords:
+    """Records without unpacked bases (raw_bases / seq_src) -> the same records with seq and qual,
+    one code / phred per byte at seq_off (the default decode's arrays; the other arrays shared)."""
+    if raw.seq is not None:
+        return raw
+    import dataclasses
+    l = raw.l_seq.astype(np.int64)
+    n = int(l.sum())
+    rec = np.repeat(np.arange(raw.n, dtype=np.int64), l)
+    off = np.cumsum(l) - l
+    j = np.arange(n, dtype=np.int64) - np.repeat(off, l)
+    src = raw.seq_src[:raw.n].astype(np.int64)
+    b = raw.raw_bases[src[rec] + (j >> 1)] if n else np.zeros(0, np.uint8)
+    seq = np.where(j & 1, b & 15, b >> 4).astype(np.uint8)
+    qual = raw.raw_bases[(src + (l + 1) // 2)[rec] + j] if n else np.zeros(0, np.uint8)
+    return dataclasses.replace(raw, seq_off=off, seq=seq, qual=np.ascontiguousarray(qual), raw_bases=None,
+                               seq_src=None)
+
+
+def pack_bases(raw: RawRecords, lead: int = 0, gap: int = 0) -> RawRecords:
+    """Records with seq and qual -> the form a decode without unpacked bases gives: every record's
+    SEQ field packed as in the BAM, then its QUAL field, back to back in raw_bases from byte `lead`,
+    `gap` unused bytes between records (tests: any alignment of a record's SEQ)."""
+    if raw.seq is None:
+        return raw
+    import dataclasses
+    l = raw.l_seq.astype(np.int64)
+    size = (l + 1) // 2 + l + gap
+    src = lead + np.cumsum(size) - size
+    total = int(lead + size.sum())
+    buf = np.zeros(total + 1, np.uint8)
+    rec = np.repeat(np.arange(raw.n, dtype=np.int64), l)
+    j = np.arange(int(l.sum()), dtype=np.int64) - np.repeat(np.cumsum(l) - l, l)
+    so = np.repeat(raw.seq_off.astype(np.int64), l) + j
+    code = raw.seq[so].astype(np.uint8) & 15
+    np.bitwise_or.at(buf, src[rec] + (j >> 1), np.where(j & 1, code, code << 4).astype(np.uint8))
+    buf[(src + (l + 1) // 2)[rec] + j] = raw.qual[so]
+    return dataclasses.replace(raw, seq=None, qual=None, raw_bases=buf[:total],
+                               seq_src=np.concatenate([src, [total]]).astype(np.int64))
 
 
 def records_from_dicts(recs: Sequence[dict]) -> RawRecords:

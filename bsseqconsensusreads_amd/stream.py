@@ -52,7 +52,11 @@ class StreamJob:
     `fastq`, an Engine stream only.
     gpu_bam: the output BAM's records are written in HBM from the consensus (Engine.bam_records),
     checksummed and deflated there (bgzf.BamWriter.add_device): the file of a gpu_bgzf run, byte
-    for byte; needs `out_bam`, an Engine stream only; implies the GPU deflate for the BAM."""
+    for byte; needs `out_bam`, an Engine stream only; implies the GPU deflate for the BAM.
+    gpu_image: the chunks are decoded without unpacked bases (bam.StreamChunk.decode(packed=True)),
+    their SEQ / QUAL bytes go up once a chunk and every batch's family images are made in HBM from
+    them (Engine.image, bsdc_image_gather) instead of on the host: the same images, so the same
+    output files; an Engine stream only.  A split_ext chunk unpacks its bases on the host."""
 
     in_bam: str
     fasta: Optional[str]
@@ -79,6 +83,7 @@ class StreamJob:
     regions: bool = False
     gpu_fastq: bool = False
     gpu_bam: bool = False
+    gpu_image: bool = False
     gpu_inflate: bool = False  # (stays the last field)
 
 
@@ -95,6 +100,7 @@ class Chunk:
     splices: Optional[np.ndarray] = None
     pool_buf: Optional[np.ndarray] = None
     results: Sequence = ()
+    pin_buf: object = None  # (gpu_image) the pinned tensor raw.raw_bases lies in (PinnedRaw)
 
 
 class Fault:
@@ -121,14 +127,36 @@ def plan_molecular(raw):
     return raw, pipeline.plan_families(raw, "vote", family_order="mi-group")
 
 
+class PinnedRaw:
+    """Pinned host buffers for the chunks' SEQ / QUAL bytes (RawRecords.raw_bases, gpu_image): the
+    reader take()s one per chunk, the upload from it runs asynchronously, and it is give()n back
+    once the chunk's output is written (its batches were fetched, so the copy is done)."""
+
+    def __init__(self):
+        self.free, self.lock = [], threading.Lock()
+
+    def take(self, nbytes: int):
+        import torch
+        with self.lock:
+            fit = [i for i, t in enumerate(self.free) if t.numel() >= nbytes]
+            if fit:
+                return self.free.pop(min(fit, key=lambda i: self.free[i].numel()))
+        return torch.empty(max(int(nbytes * 1.15), 1), dtype=torch.uint8, pin_memory=True)
+
+    def give(self, t):
+        if t is not None:
+            with self.lock:
+                self.free.append(t)
+
+
 class PinnedBatches:
     """A chunk's batches materialized into pinned memory: chunk k's into pool k % 3 -- chunk k - 3
     is done on the GPU by then (the planner handed chunk k - 1 over only after the GPU stage took
     chunk k - 2).  A loading engine's first chunks (ranks._LazyEngine) materialize into plain host
     arrays, the pools come with it."""
 
-    def __init__(self, engine):
-        self.engine, self.k = engine, 0
+    def __init__(self, engine, gather: bool = False):
+        self.engine, self.k, self.gather = engine, 0, gather  # gather: no host images (gpu_image)
         self.pools = [] if getattr(engine, "lazy", False) else self._new()
 
     def _new(self):
@@ -136,6 +164,8 @@ class PinnedBatches:
         return [PinnedPool() for _ in range(3)]
 
     def __call__(self, plan, ranges):
+        if self.gather:
+            return pipeline.materialize_ranges(plan, ranges, gather=True)
         if not self.pools and self.engine.ready():
             self.pools = self._new()
         images = None
@@ -168,7 +198,8 @@ class FrontEnd(_Stages):
     (parse), plan, materialize, and the caller's wait for a chunk (wait); R: bam.StreamChunk.decode's."""
 
     def __init__(self, fault: Fault, source: dict, plan, build, threads: int, batch_bases: Optional[int],
-                 bufs: "bam.BufferPool", spill: Optional[str] = None):
+                 bufs: "bam.BufferPool", spill: Optional[str] = None, pinned: Optional[PinnedRaw] = None):
+        self.pinned = pinned  # (gpu_image) decode without unpacked bases, raw_bases into its buffers
         self.fault, self.source, self.plan, self.build = fault, dict(source), plan, build
         self.source.setdefault("stats", {})
         self.threads, self.batch_bases, self.bufs, self.spill = threads, batch_bases, bufs, spill
@@ -223,10 +254,18 @@ class FrontEnd(_Stages):
                     ch.discard()
                     continue  # drain to the decoder's None without parsing
                 t1 = time.perf_counter()
-                raw = ch.decode(self.threads, self.R, self.bufs)[1]
+                pin_t = []
+                if self.pinned is not None:
+                    def pin(nbytes):
+                        pin_t.append(self.pinned.take(nbytes))
+                        return pin_t[0].numpy()
+                    raw = ch.decode(self.threads, self.R, self.bufs, packed=True, pin=pin)[1]
+                else:
+                    raw = ch.decode(self.threads, self.R, self.bufs)[1]
                 self.T["parse"] += time.perf_counter() - t1
                 self.T["reader_wait"] += t1 - t0
-                self.parsed.put(Chunk(raw, splices=ch.splices, pool_buf=ch.pool_buf))
+                self.parsed.put(Chunk(raw, splices=ch.splices, pool_buf=ch.pool_buf,
+                                      pin_buf=pin_t[0] if pin_t else None))
         except BaseException as e:  # noqa: BLE001
             self.fault(e)
             for ch in iter(self.raws.get, None):  # let the decoder finish
@@ -423,15 +462,16 @@ def step5_stream(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, p
                  chunk_bytes: int = bam.DEFAULT_CHUNK_BYTES, slack: int = bam.DEFAULT_SLACK,
                  batch_bases: Optional[int] = None, stats: Optional[dict] = None, gpu_bgzf: bool = False,
                  defer: Optional[int] = None, read_size: int = 8 << 20, filter=None, gpu_inflate: bool = False,
-                 gpu_fastq: bool = False, gpu_bam: bool = False) -> dict:
+                 gpu_fastq: bool = False, gpu_bam: bool = False, gpu_image: bool = False) -> dict:
     """step5 in bounded memory, pipelined (run); defer: the span past which a template is
     deferred (default DEFAULT_DEFER_SPAN; 0 = off); read_size: compressed bytes per refill;
     filter: as step5's; gpu_inflate: the input's BGZF blocks inflate on the GPU (bgzf.GpuInflate);
     gpu_fastq: the FASTQ pair is formatted, checksummed and deflated on the GPU (StreamJob);
-    gpu_bam: the BAM's records are written, checksummed and deflated on the GPU (StreamJob)."""
+    gpu_bam: the BAM's records are written, checksummed and deflated on the GPU (StreamJob);
+    gpu_image: the family images are made on the GPU from the records' bytes (StreamJob)."""
     job = StreamJob(in_bam, fasta, out_bam, fastq, prefix, threads, level, tags, gpu_bgzf, chunk_bytes, slack,
                     batch_bases, read_size, filter=filter, defer=defer, gpu_inflate=gpu_inflate, gpu_fastq=gpu_fastq,
-                    gpu_bam=gpu_bam)
+                    gpu_bam=gpu_bam, gpu_image=gpu_image)
     return _public(run(job, engine, stats=stats))
 
 
@@ -439,7 +479,8 @@ def molecular_stream(in_bam: str, out_bam: Optional[str], engine=None, prefix: O
                      level: int = 6, fastq: Optional[Tuple[str, str]] = None, tags: bool = True,
                      chunk_bytes: int = bam.DEFAULT_CHUNK_BYTES, batch_bases: Optional[int] = None,
                      stats: Optional[dict] = None, gpu_bgzf: bool = False, min_consensus_base_quality: int = 0,
-                     filter=None, gpu_inflate: bool = False, gpu_fastq: bool = False, gpu_bam: bool = False) -> dict:
+                     filter=None, gpu_inflate: bool = False, gpu_fastq: bool = False, gpu_bam: bool = False,
+                     gpu_image: bool = False) -> dict:
     """Rule call_consensus_reads_molecular (main.snake.py:46-55) in bounded memory: the same
     pipeline as step5_stream over a GroupReadsByUmi-ordered input cut between MI runs
     (stream_chunks(runs=True)); each chunk's runs are its consensus families (pipeline.molecular_records,
@@ -448,7 +489,7 @@ def molecular_stream(in_bam: str, out_bam: Optional[str], engine=None, prefix: O
     (main.snake.py:54, README.md:83); this holds about six chunks."""
     job = StreamJob(in_bam, None, out_bam, fastq, prefix, threads, level, tags, gpu_bgzf, chunk_bytes,
                     batch_bases=batch_bases, molecular=int(min_consensus_base_quality), filter=filter,
-                    gpu_inflate=gpu_inflate, gpu_fastq=gpu_fastq, gpu_bam=gpu_bam)
+                    gpu_inflate=gpu_inflate, gpu_fastq=gpu_fastq, gpu_bam=gpu_bam, gpu_image=gpu_image)
     return _public(run(job, engine, stats=stats))
 
 
@@ -599,8 +640,9 @@ def _run_chunk(eng, runner, ch: Chunk, mode: int, tags: bool, job: StreamJob, G:
             sub = R.take(ch.raw, fb.src) if getattr(runner, "needs_raw", False) else None
             parts.append(pipeline.consensus_from_output(fb, runner.run_batch(fb, mode, tags, sub)))
         return pipeline.concat_consensus(parts)
-    if ch.batches is None:
-        return pipeline.run_step5(eng, ch.raw, tags=tags, batch_bases=job.batch_bases, filter=job.filter)[0]
+    if ch.batches is None:  # (gpu_image: the whole-chunk path reads unpacked bases)
+        return pipeline.run_step5(eng, R.unpack_bases(ch.raw), tags=tags, batch_bases=job.batch_bases,
+                                  filter=job.filter)[0]
     fkw = {} if job.filter is None else {"filter": job.filter, "molecular": job.molecular is not None}
     raw = ch.raw
     names = lambda fb: bam.family_names(fb.fam_mi, raw.mi_names, job.prefix)  # noqa: E731
@@ -612,6 +654,8 @@ def _run_chunk(eng, runner, ch: Chunk, mode: int, tags: bool, job: StreamJob, G:
         fkw.update(bam_tables=lambda fb: (names(fb), bam.family_aux(fb.fam_off, fb.src, fb.fam_mi, raw, job.threads)),
                    bam_tags=job.tags, seqqual=host_out, molecular=job.molecular is not None)
         tags = False
+    if job.gpu_image:  # the batches carry no images: they are made in HBM from the chunk's bytes
+        fkw.update(raw_bases=raw.raw_bases)
     return pipeline.concat_consensus(pipeline.run_batches(eng, ch.batches, mode, tags, G, **fkw))
 
 
@@ -643,6 +687,10 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
         if job.gpu_bgzf or molecular or job.filter is not None or job.gpu_inflate or job.gpu_fastq or job.gpu_bam:
             raise ValueError("a runner stream: step 5 with host inflate and deflate only, unfiltered "
                              "(no gpu_bgzf, gpu_inflate, gpu_fastq or gpu_bam)")
+        if job.gpu_image:
+            raise ValueError("a runner stream makes the family images on the host (no gpu_image)")
+    if job.gpu_image and (job.rng is not None or job.owner is not None):
+        raise ValueError("gpu_image is not supported in a rank's stream yet (one process, one GPU)")
     if job.gpu_fastq and job.fastq is None:
         raise ValueError("gpu_fastq needs the FASTQ pair (fastq=(path1, path2))")
     if job.gpu_bam and job.out_bam is None:
@@ -690,15 +738,17 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
         source = dict(path=job.in_bam, threads=job.threads, chunk_bytes=job.chunk_bytes, slack=job.slack,
                       read_size=job.read_size, runs=molecular, rng=job.rng, stats=rs, owner=job.owner, defer=dspan,
                       keys=late is not None, inflater=inflater)
+        pinned = PinnedRaw() if job.gpu_image else None
         front = FrontEnd(fault, source, plan_molecular if molecular else functools.partial(plan_step5, ref=ref),
-                         pipeline.materialize_ranges if runner is not None else PinnedBatches(eng), job.threads,
-                         job.batch_bases, bufs, spill_path)
+                         pipeline.materialize_ranges if runner is not None else PinnedBatches(eng, job.gpu_image),
+                         job.threads, job.batch_bases, bufs, spill_path, pinned=pinned)
         back = BackEnd(fault, out_bam, fastq, header, prefix, job.threads, job.level, bufs, molecular,
                        (lambda: eng.device) if job.gpu_bgzf else None,
                        "first" if (solo and dspan) else job.fragment, marks, k_first,
                        tie=0 if late is not None else 1,  # (a spill piece sorts before the stream's piece of its key)
                        fq_device=(lambda: eng.device) if job.gpu_fastq else None,
-                       bam_device=(lambda: eng.device) if job.gpu_bam else None)
+                       bam_device=(lambda: eng.device) if job.gpu_bam else None,
+                       on_written=(lambda ch: pinned.give(ch.pin_buf)) if pinned is not None else None)
         pjob = dataclasses.replace(job, prefix=prefix)  # (the read names' prefix, resolved)
         mode = pipeline.MODE_VOTE if molecular else pipeline.MODE_CONVERT | pipeline.MODE_EXTEND | pipeline.MODE_VOTE
         tg = job.tags and out_bam is not None  # the FASTQ pair carries no tags

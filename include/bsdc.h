@@ -389,6 +389,40 @@ int32_t bsdc_bam_format(const bsdc_consensus *out, const uint8_t *filt, int32_t 
                         const int64_t *aux_off, const uint8_t *aux_buf, const int64_t *aux_off_host, int64_t *off,
                         uint8_t *rec, int64_t cap, uint8_t *tmp, void *stream);
 
+/* (new exports, ABI 19 still) The family images gathered on the device from the records' SEQ and
+ * QUAL bytes as they lie in the BAM (replaces the host's unpack of htsjdk-style record bytes into
+ * per-base arrays and their copy into the batch, behind CallDuplexConsensusReads /
+ * CallMolecularConsensusReads --input, main.snake.py:46-55,155-164; csrc/bsdc_image.hip, DESIGN.md
+ * section 8.9).  raw[0, n_raw): for every record its SEQ field ((l_seq + 1) / 2 bytes, two nt16
+ * codes a byte, high nibble first) followed by its QUAL field (l_seq bytes), at any byte offset.
+ * One bsdc_image_rec per batch record; the output is the bsdc_family_batch's seq [n_slots / 2] and
+ * qual [n_slots]: record bases skip .. skip + len - 1 at nibbles / bytes slot + 1 .. slot + len,
+ * every other byte of both images 0 -- the bytes libbsdc_io's bsdc_materialize_fill and
+ * bsdc_split_move make from unpacked bases.  n_slots is a multiple of 8; raw, seq_img and qual_img
+ * are 4-byte aligned.  bsdc_image_gather: device pointers but for recs_host, the caller's host
+ * copy of the table, which is what gets checked; the images are zeroed and filled on `stream`
+ * (hipStream_t); returns 0 once enqueued.  BSDC_EINVAL, before anything is enqueued, naming the
+ * record and the field (bsdc_last_error of the context; bsdc_image_last_error, thread-local, also
+ * without one): src or src + (l_seq + 1) / 2 + l_seq outside [0, n_raw]; skip + len > l_seq or a
+ * negative one; slot % 4 != 0; slot + 1 + len > n_slots.  The kernel makes the same test per entry
+ * and skips a bad one, and reads and writes inside the three buffers whatever the table holds.
+ * bsdc_image_gather_host: host pointers, the same per-dword function run sequentially on the CPU
+ * (no GPU needed; ctx may be NULL) -- the twin the tests compare the kernel with. */
+typedef struct {
+    int64_t src;    /* byte offset of the record's SEQ field in raw; QUAL at src + (l_seq + 1) / 2 */
+    int32_t l_seq;  /* the record's length */
+    int32_t skip;   /* leading bases dropped (the plan's sL) */
+    int32_t len;    /* bases kept (the plan's L) */
+    uint32_t slot;  /* the record's batch slot, a multiple of 4 */
+} bsdc_image_rec;
+
+int32_t bsdc_image_gather(bsdc_ctx *ctx, const uint8_t *raw, int64_t n_raw, const bsdc_image_rec *recs,
+                          const bsdc_image_rec *recs_host, int64_t n_rec, int64_t n_slots, uint8_t *seq_img,
+                          uint8_t *qual_img, void *stream);
+int32_t bsdc_image_gather_host(bsdc_ctx *ctx, const uint8_t *raw, int64_t n_raw, const bsdc_image_rec *recs,
+                               int64_t n_rec, int64_t n_slots, uint8_t *seq_img, uint8_t *qual_img);
+const char *bsdc_image_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

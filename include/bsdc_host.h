@@ -15,6 +15,8 @@
 #define BSDC_HOST_H
 #include <stdint.h>
 
+#include "bsdc.h" /* bsdc_image_rec */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -23,7 +25,11 @@ extern "C" {
 #define BSDC_PLAN_VOTE 1 /* tool-2 output: the vote alone */
 #define BSDC_PLAN_EMISSING_MI (-61) /* a kept record has no MI tag (tools/2.extend_gap.py:179-180) */
 
-/* Decoded records, structure of arrays (records.RawRecords).  seq holds one nt16 code per byte. */
+/* Decoded records, structure of arrays (records.RawRecords).  seq holds one nt16 code per byte.
+ * Records decoded without unpacked bases (bsdc_bam_arrays.raw_bases, include/bsdc_io.h) have seq
+ * and qual NULL and raw_bases / seq_src set instead: record k's SEQ field, packed as in the BAM,
+ * at raw_bases + seq_src[k].  The plan then reads the one base it needs (tool 1's RD prediction)
+ * from there, and bsdc_materialize_fill takes no images (bsdc_batch_arrays.image_rec). */
 typedef struct bsdc_host_records {
     int64_t n;
     const uint16_t *flag;
@@ -40,6 +46,8 @@ typedef struct bsdc_host_records {
     const int32_t *mc_n;
     const uint32_t *mc_cigar;
     const int64_t *mi_rank, *name_rank; /* byte-order sort keys of the MI bases / names (NULL: the ids) */
+    const uint8_t *raw_bases;           /* with seq == NULL: the records' SEQ + QUAL fields as in the BAM */
+    const int64_t *seq_src;             /* [n] byte offset of record k's SEQ field in raw_bases */
 } bsdc_host_records;
 
 typedef struct bsdc_host_reference {
@@ -85,8 +93,12 @@ typedef struct bsdc_batch_sizes {
     int32_t max_len;
 } bsdc_batch_sizes;
 
-/* Device-batch arrays of families [f0, f1) (batch.FamilyBatch); seq [n_slots / 2] and qual
- * [n_slots] must be zeroed by the caller. */
+/* Device-batch arrays of families [f0, f1) (batch.FamilyBatch); the fill writes every byte of seq
+ * [n_slots / 2] and qual [n_slots].  seq and qual NULL: no images are made (the records may then
+ * lack unpacked bases); image_rec, when not NULL, receives the table bsdc_image_gather
+ * (include/bsdc.h) makes them from on the device: per batch record src = seq_src (0 for records
+ * with unpacked bases), l_seq, skip = sL, len = L, slot = the record's slot before any
+ * bsdc_split_move (the caller rewrites that column after it). */
 typedef struct bsdc_batch_arrays {
     uint8_t *seq, *qual;          /* packed nt16 image / quals, slot layout */
     uint32_t *rec;                /* [4 n_rec] slot, pos, len | flag << 16, link */
@@ -100,6 +112,7 @@ typedef struct bsdc_batch_arrays {
     int64_t *need_l, *img;        /* [n_fam] large arena bytes, image bytes */
     int8_t *cls;                  /* [n_fam] small bucket q, or BSDC_SMALL_BUCKETS + large bucket */
     const int64_t *large_caps;    /* [BSDC_LARGE_BUCKETS - 1] LDS arena caps of the large buckets */
+    bsdc_image_rec *image_rec;    /* [n_rec] or NULL */
 } bsdc_batch_arrays;
 
 /* Sizes the batch of plan families [f0, f1) (mode_full: tool 1 + 2 run in the launch). */
@@ -125,7 +138,8 @@ void bsdc_batch_free(bsdc_batch *b);
  * record first: the whole-family fallback reads the image from its slot); a part stages the
  * 32-entry chunks that cover its records, from its first slot rounded down to 32 (the staged image
  * entries).  bsdc_split_move then moves the bytes of seq (packed nt16) and qual and rewrites the
- * batch records' slots (rec_off [n_rec]); split_fams: [n_sf][8] (include/bsdc.h). */
+ * batch records' slots (rec_off [n_rec]); split_fams: [n_sf][8] (include/bsdc.h).  seq and qual NULL:
+ * only the slots are rewritten (the images are gathered on the device afterwards). */
 int64_t bsdc_split_count(const uint32_t *rec, const uint32_t *ents, int64_t n_ent, int64_t part_cap, int32_t max_part_rec,
                          int32_t *nparts, int64_t *nrecs, int32_t n_threads);
 void bsdc_split_fill(const uint32_t *rec, const uint32_t *ents, int64_t n_ent, int64_t part_cap, int32_t max_part_rec,

@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define BSDC_IO_ABI_VERSION 15
+#define BSDC_IO_ABI_VERSION 16
 #define BSDC_IO_EFORMAT (-10) /* not BGZF/BAM, truncated, bad CRC */
 #define BSDC_IO_EIO (-11)     /* open/read/write failed */
 #define BSDC_IO_EINVAL (-22)  /* bad argument */
@@ -68,6 +68,13 @@ typedef struct {
     int64_t *ref_len;       /* [n_ref] */
     int64_t *ref_name_off;  /* [n_ref + 1] */
     char *ref_name_buf;
+    /* (ABI 16) decode without unpacked bases: with raw_bases not NULL, seq and qual are not written
+     * (they may be NULL); each record's SEQ field ((l_seq + 1) / 2 bytes, packed as in the file)
+     * and QUAL field (l_seq bytes) go back to back into raw_bases instead, record k's SEQ at
+     * raw_bases + seq_src[k]; seq_src [n + 1], the last one the bytes written: at most
+     * n_bases + (n_bases + n_rec) / 2.  What bsdc_image_gather (include/bsdc.h) reads. */
+    uint8_t *raw_bases;
+    int64_t *seq_src;
 } bsdc_bam_arrays;
 
 int32_t bsdc_io_abi_version(void);

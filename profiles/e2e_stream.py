@@ -5,6 +5,9 @@ synthetic coordinate-sorted C2 BAM + FASTA on local disk, then, each in a fresh 
   stream  bam.step5_stream: bounded chunks, reader / GPU / writer threads overlapped
   stream_fastq  the same, writing the FASTQ pair of the next rule instead of the BAM
   stream_gpubgzf, stream_fastq_gpubgzf  the same with the BGZF deflate on the GPU
+  stream_fastq_gpuimage  stream_fastq_gpufastq with the family images made on the GPU (--gpu-image,
+          DESIGN.md 8.9); stream_bam_gpubam, stream_bam_gpuimage  the BAM with --gpu-bam, without and
+          with --gpu-image
   fleet   fleet.step5_stream_multi: this child reads and writes, --workers spawned GPU worker
           processes (all on GPU 0 on a one-GPU box; started before the clock) run the batches
   fleet_gpubgzf  the same with the writer's deflate on GPU 0
@@ -110,14 +113,20 @@ def child(args):
         info = bam.molecular(args.grouped, args.out, engine=eng, threads=args.threads, level=args.level)
     elif args.mode == "whole":
         info = bam.step5(args.inp, args.fa, args.out, engine=eng, threads=args.threads, level=args.level)
-    elif args.mode in ("stream_fastq", "stream_fastq_gpubgzf", "stream_fastq_gpufastq"):  # the fused FASTQ emission
+    elif args.mode in ("stream_bam_gpubam", "stream_bam_gpuimage"):  # the BAM's records written on the GPU
+        info = bam.step5_stream(args.inp, args.fa, args.out, engine=eng, threads=args.threads, level=args.level,
+                                chunk_bytes=args.chunk_mb << 20, stats=stats, gpu_bam=True,
+                                gpu_image=args.mode == "stream_bam_gpuimage")
+    elif args.mode in ("stream_fastq", "stream_fastq_gpubgzf", "stream_fastq_gpufastq",
+                       "stream_fastq_gpuimage"):  # the fused FASTQ emission
         # (main.snake.py:167-177), no BAM; _gpubgzf: its blocks deflated on the GPU; _gpufastq: its
         # text formatted and checksummed there too
         info = bam.step5_stream(args.inp, args.fa, None, engine=eng, threads=args.threads, level=args.level,
                                 fastq=(args.out + ".1.fq.gz", args.out + ".2.fq.gz"),
                                 chunk_bytes=args.chunk_mb << 20, stats=stats,
                                 gpu_bgzf=args.mode == "stream_fastq_gpubgzf",
-                                gpu_fastq=args.mode == "stream_fastq_gpufastq")
+                                gpu_fastq=args.mode in ("stream_fastq_gpufastq", "stream_fastq_gpuimage"),
+                                gpu_image=args.mode == "stream_fastq_gpuimage")
     else:  # stream, or stream_gpubgzf: the BAM's blocks deflated on the GPU (bam.GpuBgzf)
         info = bam.step5_stream(args.inp, args.fa, args.out, engine=eng, threads=args.threads, level=args.level,
                                 chunk_bytes=args.chunk_mb << 20, stats=stats, gpu_bgzf=args.mode == "stream_gpubgzf")
@@ -182,11 +191,19 @@ def main():
         outs[mode] = out
         print(mode, json.dumps(r), flush=True)
     bams = [open(outs[m], "rb").read() for m in outs if not m.startswith("stream_fastq") and "gpubgzf" not in m
-            and not m.startswith("molecular") and not m.startswith("ranks")]
+            and not m.startswith("molecular") and not m.startswith("ranks") and not m.startswith("stream_bam_")]
+    base = lambda m: m.split("@")[0]  # noqa: E731
+    for a_, b_, key, sfx in (("stream_bam_gpubam", "stream_bam_gpuimage", "bam_gpuimage_bytes_identical", ("",)),
+                             ("stream_fastq_gpufastq", "stream_fastq_gpuimage", "fastq_gpuimage_bytes_identical",
+                              (".1.fq.gz", ".2.fq.gz"))):
+        xa, xb = [m for m in outs if base(m) == a_], [m for m in outs if base(m) == b_]
+        if xa and xb:  # the option changes no byte
+            res[key] = all(open(outs[xa[0]] + x, "rb").read() == open(outs[m] + x, "rb").read()
+                           for m in xa + xb for x in sfx)
     if "ranks" in outs and "stream" in outs:  # other BGZF blocks at the rank seams: the bytes inside
         import gzip
         res["ranks_bytes_identical"] = gzip.open(outs["ranks"]).read() == gzip.open(outs["stream"]).read()
-    res["outputs_identical"] = all(b == bams[0] for b in bams)
+    res["outputs_identical"] = all(b == bams[0] for b in bams) if bams else None
     gz = [open(outs[m], "rb").read() for m in ("stream_gpubgzf", "fleet_gpubgzf") if m in outs]
     if len(gz) == 2:  # the same GPU-deflated blocks from one GPU and from the fleet's writer
         res["gpubgzf_fleet_identical"] = gz[0] == gz[1]
