@@ -97,7 +97,11 @@ constexpr int kSmallMaxWaves = 8;              // wavefronts (families) per smal
 // C2 3.08 -> 3.50 ms with VGPR spills, 3.18-3.21 ms with fewer staging loads (profiles/r04/ab_c/
 // README.md), and 3.09 against 2.94-2.95 ms with 54 SGPRs spilled (profiles/r06/README.md, r6zi).
 constexpr int kSmallMinWaves = 6;              // occupancy target the register budget is cut for
-constexpr int kSmallSimdWaves = 7;             // waves per SIMD its registers allow
+// wavefronts per workgroup it is launched with (bsdc_run).  The kernel takes any count up to
+// kSmallMaxWaves from blockDim, and its launch bounds stay at that maximum: the register budget
+// above was measured under them, and a build bounded at 256 threads has not been measured.
+constexpr int kSmallWgWaves = 4;
+static_assert(kSmallWgWaves <= kSmallMaxWaves, "k_small's launch bounds");
 constexpr int kLdsBytes = 160 * 1024;           // LDS per CU
 constexpr double kLrScale = 1048576.0;          // 2^20
 constexpr int kSqBuckets = 136;                 // phred buckets of S: 4 per octave over [2^-32, 4)
@@ -3253,7 +3257,7 @@ int32_t bsdc_run(bsdc_ctx *c, const bsdc_family_batch *b, bsdc_consensus *o, int
     for (int q = 0; q < BSDC_SMALL_BUCKETS; q++) {
         if (b->n_small[q] > 0 &&
             (b->small_arena[q] % 16 || b->small_arena[q] <= 0 ||
-             (size_t)kTabBytes + 2 * (size_t)kArenaGuard + 4 * (size_t)b->small_arena[q] > kLdsBytes)) {
+             (size_t)kTabBytes + 2 * (size_t)kArenaGuard + kSmallWgWaves * (size_t)b->small_arena[q] > kLdsBytes)) {
             c->err = "bad small arena size";
             return BSDC_EINVAL;
         }
@@ -3336,15 +3340,15 @@ int32_t bsdc_run(bsdc_ctx *c, const bsdc_family_batch *b, bsdc_consensus *o, int
         for (int q = 0; q < BSDC_SMALL_BUCKETS && rc == 0; q++) {
             const int64_t nf = b->n_small[q];
             if (nf > 0) {
-                // wavefronts per workgroup (they share one copy of the tables): 4 or 8, whichever
-                // keeps more wavefronts resident per CU; the smaller on a tie
-                // (a workgroup's wavefronts spread over the 4 SIMDs: at most kSmallSimdWaves each)
-                const int64_t a = b->small_arena[q];
-                const int64_t g2 = 2 * kArenaGuard;
-                const int64_t w4 = 4 * std::min<int64_t>(kSmallSimdWaves, kLdsBytes / (kTabBytes + g2 + 4 * a));
-                const int64_t w8 = 8 * std::min<int64_t>(kSmallSimdWaves / 2, kLdsBytes / (kTabBytes + g2 + 8 * a));
-                const int nw = w8 > w4 ? 8 : 4;
-                const size_t lds = (size_t)nw * (size_t)a + (size_t)g2;  // + the static tables
+                // wavefronts per workgroup (they share one copy of the tables): 4 for every class.
+                // A count of the wavefronts the LDS keeps resident per CU gave the 6144-B class 8
+                // (24 against 20); measured it is the other way round, since a workgroup's LDS
+                // returns only when its slowest wavefront ends: that class alone on C2, 331 us at
+                // 8 against 280 at 4, 3.32 against 4.45 wavefronts in flight per SIMD, and C2's
+                // step 2.86 -> 2.79 ms.  2 loses on the step (3.10 ms); each class alone at 2, 4
+                // and 8: profiles/occupancy/README.md
+                const int nw = kSmallWgWaves;
+                const size_t lds = (size_t)nw * (size_t)b->small_arena[q] + 2 * (size_t)kArenaGuard;  // + the static tables
                 const hipStream_t ls = next_stream();
                 if (rc) break;
                 launch_small(tg, nw, lds, ls, P, f, nf, b->small_arena[q]);
