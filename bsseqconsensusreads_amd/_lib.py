@@ -72,7 +72,8 @@ EXPORTS = ("bsdc_abi_version", "bsdc_ctx_create", "bsdc_ctx_set_params", "bsdc_c
            "bsdc_bgzf_deflate", "bsdc_bgzf_pack", "bsdc_host_register", "bsdc_host_unregister", "bsdc_filter",
            "bsdc_bgzf_inflate", "bsdc_bgzf_inflate_host", "bsdc_fastq_text_bound", "bsdc_fastq_tmp_bytes",
            "bsdc_fastq_format", "bsdc_bgzf_crc32", "bsdc_bam_bytes_bound", "bsdc_bam_tmp_bytes", "bsdc_bam_format",
-           "bsdc_image_gather", "bsdc_image_gather_host", "bsdc_image_last_error")
+           "bsdc_image_gather", "bsdc_image_gather_host", "bsdc_image_last_error", "bsdc_metrics_words", "bsdc_metrics",
+           "bsdc_metrics_filter", "bsdc_metrics_host", "bsdc_metrics_filter_host", "bsdc_metrics_last_error")
 
 _lib = None
 
@@ -159,6 +160,19 @@ def load(path: str = LIB_PATH):
                                            C.c_void_p, C.c_void_p]
     lib.bsdc_image_gather_host.restype = C.c_int32
     lib.bsdc_image_last_error.restype = C.c_char_p
+    lib.bsdc_metrics_words.argtypes = [C.c_int32]
+    lib.bsdc_metrics_words.restype = C.c_int64
+    lib.bsdc_metrics.argtypes = [C.c_void_p, C.POINTER(ConsensusC), C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                 C.c_void_p]
+    lib.bsdc_metrics.restype = C.c_int32
+    lib.bsdc_metrics_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.bsdc_metrics_filter.restype = C.c_int32
+    lib.bsdc_metrics_host.argtypes = [C.c_void_p, C.POINTER(ConsensusC), C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                      C.c_void_p]
+    lib.bsdc_metrics_host.restype = C.c_int32
+    lib.bsdc_metrics_filter_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.bsdc_metrics_filter_host.restype = C.c_int32
+    lib.bsdc_metrics_last_error.restype = C.c_char_p
     if lib.bsdc_abi_version() != BSDC_ABI_VERSION:
         raise RuntimeError("libbsdc ABI %d != %d" % (lib.bsdc_abi_version(), BSDC_ABI_VERSION))
     if path == LIB_PATH:

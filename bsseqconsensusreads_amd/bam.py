@@ -1014,7 +1014,7 @@ def duplex_records(cons, raw: R.RawRecords, prefix: str, threads: int = 0, molec
 
 
 def consensus_sharded(eng, raw: R.RawRecords, tags: bool, batch_bases: Optional[int] = None, dist=None,
-                      filter=None):
+                      filter=None, metrics: bool = False):
     """pipeline.run_step5 over the ranks of `dist` (None = this process alone): every rank forms
     the same family plan, runs the batches shard.deal gives it on its own GPU, and rank 0 gets the
     consensus of all batches in plan order (shard.gather_in_order; other ranks get None).  A plan
@@ -1022,9 +1022,12 @@ def consensus_sharded(eng, raw: R.RawRecords, tags: bool, batch_bases: Optional[
     two-launch fallback)."""
     from . import pipeline, shard
     if dist is None or dist.get_world_size() == 1:
-        return pipeline.run_step5(eng, raw, tags=tags, batch_bases=batch_bases, filter=filter)[0]
+        mkw = {"metrics": True} if metrics else {}
+        return pipeline.run_step5(eng, raw, tags=tags, batch_bases=batch_bases, filter=filter, **mkw)[0]
     if filter is not None:
         raise ValueError("the consensus filter is not supported with several ranks yet")
+    if metrics:
+        raise ValueError("metrics is not supported with several ranks yet")
     rank, world = dist.get_rank(), dist.get_world_size()
     plan = pipeline.plan_families(raw, "full", eng.ref)
     if plan.split_ext:
@@ -1039,14 +1042,15 @@ def consensus_sharded(eng, raw: R.RawRecords, tags: bool, batch_bases: Optional[
 
 def step5(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, prefix: Optional[str] = None, threads: int = 0,
           level: int = 6, fastq: Optional[Tuple[str, str]] = None, tags: bool = True, batch_bases: Optional[int] = None,
-          dist=None, filter=None) -> dict:
+          dist=None, filter=None, metrics: Optional[str] = None, metrics_cycles: int = 512) -> dict:
     """Rules convert_Bstrain .. callduplex (main.snake.py:121-164) as one call on files; with
     `fastq`, also the following consensusduplex_to_fq rule (main.snake.py:167-177) straight from
     the consensus records (out_bam may then be None: no BAM round trip).  The stream runs as
     bounded device batches (batch_bases, pipeline.DEFAULT_BATCH_BASES); with `dist` the batches
     are shared by the ranks (one GPU each) and rank 0 writes the files.  filter (filter.FilterParams):
     fgbio FilterConsensusReads on the device between the vote and the records -- the outputs hold
-    the kept templates, masked, and the info dict a `filter` entry (filter.summary)."""
+    the kept templates, masked, and the info dict a `filter` entry (filter.summary).  metrics: the
+    path of the run's metrics JSON, reduced on the device from every batch (one rank)."""
     from .device import Engine
     header, raw = read_bam(in_bam, threads)
     ref = read_fasta(fasta, header)
@@ -1054,13 +1058,23 @@ def step5(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, prefix: 
     eng = Engine(0) if own else engine
     try:
         eng.load_reference(ref)
-        cons = consensus_sharded(eng, raw, tags and out_bam is not None, batch_bases, dist, filter)
+        if metrics is not None:
+            eng.metrics_begin(metrics_cycles)
+        mkw = {"metrics": True} if metrics is not None else {}
+        cons = consensus_sharded(eng, raw, tags and out_bam is not None, batch_bases, dist, filter, **mkw)
+        if metrics is not None:
+            _write_metrics(eng, metrics, metrics_cycles, False, filter)
     finally:
         if own:
             eng.close()
     if cons is None:  # not rank 0
         return {"records_in": raw.n}
     return _write_consensus(cons, raw, raw.n, header, prefix, out_bam, fastq, level, threads, False, filter)
+
+
+def _write_metrics(eng, path: str, cycles: int, molecular: bool, flt):
+    from . import metrics as _metrics
+    _metrics.write(path, eng.metrics_fetch(), cycles, _metrics.run_params(eng.params, molecular, flt))
 
 
 def _write_consensus(cons, raw, n_in: int, header, prefix, out_bam, fastq, level, threads, molecular, flt) -> dict:
@@ -1081,18 +1095,26 @@ def _write_consensus(cons, raw, n_in: int, header, prefix, out_bam, fastq, level
 
 def molecular(in_bam: str, out_bam: Optional[str], engine=None, prefix: Optional[str] = None, threads: int = 0,
               level: int = 6, fastq: Optional[Tuple[str, str]] = None, tags: bool = True,
-              min_consensus_base_quality: int = 0, filter=None) -> dict:
+              min_consensus_base_quality: int = 0, filter=None, metrics: Optional[str] = None,
+              metrics_cycles: int = 512) -> dict:
     """Rule call_consensus_reads_molecular (main.snake.py:46-55, fgbio CallMolecularConsensusReads)
     on files; with `fastq`, also consensus_to_fq_unfiltered (main.snake.py:58-67) -- or, with
-    `filter` (as step5's, the molecular rules), the filtered pair of consensus_to_fq (:70-80)."""
+    `filter` (as step5's, the molecular rules), the filtered pair of consensus_to_fq (:70-80).
+    metrics: as step5's."""
     from . import pipeline
     from .device import Engine
     header, raw = read_bam(in_bam, threads)
     own = engine is None
     eng = Engine(0) if own else engine
     try:
+        if metrics is not None:
+            eng.metrics_begin(metrics_cycles)
         cons, rm = pipeline.run_molecular(eng, raw, tags=tags and out_bam is not None,
-                                          min_consensus_base_quality=min_consensus_base_quality, filter=filter)
+                                          min_consensus_base_quality=min_consensus_base_quality, filter=filter,
+                                          **({"metrics": True} if metrics is not None else {}))
+        if metrics is not None:
+            with eng.flags(min_consensus_base_quality=min_consensus_base_quality):  # (the flags the run used)
+                _write_metrics(eng, metrics, metrics_cycles, True, filter)
     finally:
         if own:
             eng.close()

@@ -68,6 +68,13 @@ def parse(argv):
                        help="make the family images on the GPU from the records' SEQ / QUAL bytes instead of "
                             "unpacking and copying every base on the host (streaming, --gpus 1; the same output "
                             "files)")
+        p.add_argument("--metrics", default=None, metavar="PATH",
+                       help="write the run's consensus metrics, reduced on the GPU, as one JSON file: histograms of "
+                            "cD/aD/bD and cE/aE/bE per record, of the consensus quality, and per-cycle depth, errors, "
+                            "quality, no-calls and strand disagreements of the unfiltered consensus (--gpus 1; the "
+                            "same output files)")
+        p.add_argument("--metrics-cycles", type=int, default=512, metavar="N",
+                       help="rows of the per-cycle table, 2..1024; columns at and past N - 1 share the last row")
         p.add_argument("--batch-bases", type=int, default=None, help="device batch budget in bases")
         p.add_argument("--chunk-mb", type=int, default=64, help="--stream: record MiB per chunk")
         if name == "step5":
@@ -117,6 +124,10 @@ def parse(argv):
         ap.error("--fastq1 and --fastq2 go together")
     if a.output == "-" and a.fastq1 is None:
         ap.error("nothing to write: give OUT.bam or --fastq1/--fastq2")
+    if a.metrics is not None and getattr(a, "gpus", 1) > 1:
+        ap.error("--metrics is not supported with --gpus %d yet (one process, one GPU)" % a.gpus)
+    if not 2 <= a.metrics_cycles <= 1024:
+        ap.error("--metrics-cycles takes 2..1024")
     if a.gpu_inflate == "true" and getattr(a, "gpus", 1) > 1:
         ap.error("--gpu-inflate is not supported with --gpus %d yet (the rank processes start without torch)" % a.gpus)
     if a.gpu_fastq == "true":
@@ -239,7 +250,8 @@ def main(argv=None) -> int:
                                         fq, tags=a.output_per_base_tags == "true", chunk_bytes=a.chunk_mb << 20,
                                         batch_bases=a.batch_bases, gpu_bgzf=a.gpu_bgzf == "true", filter=flt,
                                         gpu_inflate=a.gpu_inflate == "true", gpu_fastq=a.gpu_fastq == "true",
-                                        gpu_bam=a.gpu_bam == "true", gpu_image=a.gpu_image == "true")
+                                        gpu_bam=a.gpu_bam == "true", gpu_image=a.gpu_image == "true",
+                                        metrics=a.metrics, metrics_cycles=a.metrics_cycles)
             elif a.cmd == "step5" and a.gpu_image == "true":
                 raise ValueError("--gpu-image applies to the streaming step only: %s is not coordinate-sorted "
                                  "and would be read whole" % a.input)
@@ -252,18 +264,20 @@ def main(argv=None) -> int:
             elif a.cmd == "step5":
                 info = bam.step5(a.input, a.reference, out, eng, a.read_name_prefix, a.threads, a.compression, fq,
                                  tags=a.output_per_base_tags == "true", batch_bases=a.batch_bases, dist=dist,
-                                 filter=flt)
+                                 filter=flt, metrics=a.metrics, metrics_cycles=a.metrics_cycles)
             elif a.stream == "true":
                 info = bam.molecular_stream(a.input, out, eng, a.read_name_prefix, a.threads, a.compression, fq,
                                             tags=a.output_per_base_tags == "true", chunk_bytes=a.chunk_mb << 20,
                                             batch_bases=a.batch_bases, gpu_bgzf=a.gpu_bgzf == "true",
                                             min_consensus_base_quality=a.min_consensus_base_quality, filter=flt,
                                             gpu_inflate=a.gpu_inflate == "true", gpu_fastq=a.gpu_fastq == "true",
-                                            gpu_bam=a.gpu_bam == "true", gpu_image=a.gpu_image == "true")
+                                            gpu_bam=a.gpu_bam == "true", gpu_image=a.gpu_image == "true",
+                                            metrics=a.metrics, metrics_cycles=a.metrics_cycles)
             else:
                 info = bam.molecular(a.input, out, eng, a.read_name_prefix, a.threads, a.compression, fq,
                                      tags=a.output_per_base_tags == "true",
-                                     min_consensus_base_quality=a.min_consensus_base_quality, filter=flt)
+                                     min_consensus_base_quality=a.min_consensus_base_quality, filter=flt,
+                                     metrics=a.metrics, metrics_cycles=a.metrics_cycles)
         finally:
             eng.close()
     except Exception as e:  # noqa: BLE001 -- the rule fails with the message, like the tools do

@@ -354,6 +354,7 @@ class Engine:
             raise RuntimeError("bsdc_ctx_create failed (%d)" % rc)
         self.ctx = h
         self.ref: Optional[Reference] = None
+        self._metrics = None  # (accumulator in HBM, cycles): metrics_begin
 
     def set_params(self, params: ConsensusParams):
         """Replace the context's flags (bsdc_ctx_set_params); later launches use them."""
@@ -465,6 +466,50 @@ class Engine:
         rc = self.lib.bsdc_filter(self.ctx, C.byref(p), 1 if molecular else 0, db.n_fam, C.byref(db._o),
                                   C.c_void_p(_dptr(db.filt)), C.c_void_p(_dptr(db.masked)), C.c_void_p(s.cuda_stream))
         self._check(rc, "bsdc_filter")
+
+    def metrics_begin(self, cycles: int = 512):
+        """The run's metrics accumulator (bsdc_metrics_words(cycles) u64 words in HBM),
+        allocated and zeroed once; `metrics` and `metrics_filter` add every batch into it."""
+        n = int(self.lib.bsdc_metrics_words(int(cycles)))
+        if n < 0:
+            raise ValueError("metrics: cycles outside 2..1024 (%r)" % (cycles,))
+        with torch.cuda.device(self.device):
+            self._metrics = (torch.zeros(n, dtype=torch.int64, device=self.device), int(cycles))
+
+    def _metrics_acc(self):
+        if self._metrics is None:
+            raise ValueError("no metrics accumulator: call Engine.metrics_begin first")
+        return self._metrics
+
+    def metrics(self, db: DeviceBatch, molecular: bool = False, stream: Optional[torch.cuda.Stream] = None):
+        """A voted batch (run with MODE_TAGS) reduced into the accumulator (bsdc_metrics), enqueued on
+        the stream that ran the vote, after it and before `filter` masks the consensus."""
+        acc, cycles = self._metrics_acc()
+        if not db.tags:
+            raise ValueError("metrics: the batch was uploaded without tags=True")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        rc = self.lib.bsdc_metrics(self.ctx, C.byref(db._o), db.n_fam, db.n_wide, 1 if molecular else 0, cycles,
+                                   C.c_void_p(_dptr(acc)), C.c_void_p(s.cuda_stream))
+        self._check(rc, "bsdc_metrics")
+
+    def metrics_filter(self, db: DeviceBatch, stream: Optional[torch.cuda.Stream] = None):
+        """The filter's outcome of a batch (db.filt, db.masked) added to the accumulator
+        (bsdc_metrics_filter), enqueued after `filter` on its stream."""
+        acc, _ = self._metrics_acc()
+        if db.filt is None:
+            raise ValueError("metrics_filter: the batch was uploaded without filt=True")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        rc = self.lib.bsdc_metrics_filter(self.ctx, C.c_void_p(_dptr(db.status)), C.c_void_p(_dptr(db.filt)),
+                                          C.c_void_p(_dptr(db.masked)), db.n_fam, C.c_void_p(_dptr(acc)),
+                                          C.c_void_p(s.cuda_stream))
+        self._check(rc, "bsdc_metrics_filter")
+
+    def metrics_fetch(self) -> np.ndarray:
+        """-> the accumulator as uint64 words (one copy, after a synchronize of the current stream:
+        at the end of the run).  The accumulator stays, so a later batch keeps adding."""
+        acc, _ = self._metrics_acc()
+        torch.cuda.current_stream(self.device).synchronize()
+        return acc.cpu().numpy().view(np.uint64).copy()
 
     def fastq(self, db: DeviceBatch, names, stream: Optional[torch.cuda.Stream] = None) -> FastqText:
         """The FASTQ text of the batch's kept families formatted where the consensus lies

@@ -301,10 +301,10 @@ def plan_ranges(plan: FamilyPlan, batch_bases: Optional[int] = None):
 
 def run_ranges(engine: Engine, plan: FamilyPlan, ranges, mode: int, tags: bool = False,
                timing: Optional[dict] = None, filter: Optional[FilterParams] = None,
-               molecular: bool = False) -> List[Consensus]:
+               molecular: bool = False, metrics: bool = False) -> List[Consensus]:
     """Plan family ranges through the kernels (run_batches), each materialized into the engine's
     staging images just before it uploads: the host builds range i + 1 while the kernels of range
-    i run.  `timing` also gets the seconds of materialize."""
+    i run.  `timing` also gets the seconds of materialize.  metrics: run_batches'."""
     import time
     T = timing if timing is not None else {}
 
@@ -314,7 +314,8 @@ def run_ranges(engine: Engine, plan: FamilyPlan, ranges, mode: int, tags: bool =
             fb = materialize(plan, a, b, images=engine.stage_images)
             T["materialize"] = T.get("materialize", 0.0) + time.perf_counter() - t0
             yield fb
-    return run_batches(engine, staged(), mode, tags, T, filter, molecular)
+    mkw = {"metrics": True} if metrics else {}
+    return run_batches(engine, staged(), mode, tags, T, filter, molecular, **mkw)
 
 
 def materialize_ranges(plan: FamilyPlan, ranges, images=None, gather: bool = False) -> List[FamilyBatch]:
@@ -328,7 +329,7 @@ def materialize_ranges(plan: FamilyPlan, ranges, images=None, gather: bool = Fal
 def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
                 timing: Optional[dict] = None, filter: Optional[FilterParams] = None,
                 molecular: bool = False, fastq_names=None, seqqual: bool = True, bam_tables=None,
-                bam_tags: bool = True, raw_bases: Optional[np.ndarray] = None) -> List[Consensus]:
+                bam_tags: bool = True, raw_bases: Optional[np.ndarray] = None, metrics: bool = False) -> List[Consensus]:
     """Materialized batches (any iterable, taken one at a time) through the kernels, one launch
     each, output per batch in order; a batch uploads and launches before the one before it is
     fetched.  `timing`: seconds added per host step (upload, fetch = wait + copy out, unpack).
@@ -343,7 +344,11 @@ def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
     handle (Consensus.bamrec); the ss rows are not fetched.
     `raw_bases` (RawRecords.raw_bases of the batches' records): batches without host images
     (materialize(gather=True)) get theirs made in HBM from it (Engine.image); it goes up once, with
-    the first batch, and is released behind the last batch's launch."""
+    the first batch, and is released behind the last batch's launch.
+    `metrics`: each batch is reduced into the engine's metrics accumulator (Engine.metrics_begin)
+    right after its vote, before a filter masks it, and the filter's outcome is added after it
+    (Engine.metrics, Engine.metrics_filter); like a filter it needs the tags' rows in
+    HBM, which are copied out only with `tags`."""
     import time
     T = timing if timing is not None else {}
     parts: List[Consensus] = []
@@ -370,11 +375,15 @@ def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
             if raw_bases is None:
                 raise ValueError("batches without host images need raw_bases (the records' SEQ / QUAL bytes)")
             raw_dev = engine.upload_raw(raw_bases)
-        db = engine.upload(fb, tags=tags or (bam_tables is not None and bam_tags), filt=filter is not None,
+        db = engine.upload(fb, tags=tags or metrics or (bam_tables is not None and bam_tags), filt=filter is not None,
                            raw_dev=raw_dev)
         engine.run(db, mode | (MODE_TAGS if db.tags else 0))
+        if metrics:
+            engine.metrics(db, molecular)
         if filter is not None:
             engine.filter(db, filter, molecular)
+            if metrics:
+                engine.metrics_filter(db)
         if fastq_names is not None:
             engine.fastq(db, fastq_names(fb))
         if bam_tables is not None:
@@ -497,37 +506,44 @@ def _cat_records(parts: List[OutRecords]) -> OutRecords:
 
 
 def run_step5(engine: Engine, raw: R.RawRecords, dump: bool = False, tags: bool = False,
-              batch_bases: Optional[int] = None, filter: Optional[FilterParams] = None):
+              batch_bases: Optional[int] = None, filter: Optional[FilterParams] = None, metrics: bool = False):
     """Rules convert_Bstrain .. callduplex (main.snake.py:121-164) -> (Consensus, tool-2 records or None).
     tags: also the single-strand reads and column statistics of fgbio's consensus tags (Consensus.ss).
     batch_bases: device batch budget (DEFAULT_BATCH_BASES); dump (the tool-2 records, parity
     tests) needs the stream in one batch.  filter: fgbio FilterConsensusReads on the device after
-    the vote (Consensus.filt / masked; seq and qual come back masked)."""
+    the vote (Consensus.filt / masked; seq and qual come back masked).  metrics: every batch adds
+    into the engine's metrics accumulator (run_batches' `metrics`; Engine.metrics_begin first)."""
     plan = plan_families(raw, "full", engine.ref)
+    mkw = {"metrics": True} if metrics else {}
     if plan.split_ext:
         # a TemplateCoordinate family lacks a record's tool-2 extension partner: run the tools as
         # their own launches (tool-2 MI groups), then callduplex on their records
         t2 = _tools_batched(engine, raw, batch_bases)
-        cons = run_duplex(engine, raw_from_records(raw, t2), tags, batch_bases, filter)
+        cons = run_duplex(engine, raw_from_records(raw, t2), tags, batch_bases, filter, **mkw)
         cons.fam_src = t2.src[cons.fam_src]  # raw2 record k is tool-2 record k
         return cons, (t2 if dump else None)
     mode = MODE_CONVERT | MODE_EXTEND | MODE_VOTE
     if dump:
         fb = materialize(plan, 0, plan.n_fam)
-        db = engine.upload(fb, dump=True, tags=tags, filt=filter is not None)
+        db = engine.upload(fb, dump=True, tags=tags or metrics, filt=filter is not None)
         engine.run(db, mode | MODE_DUMP | (MODE_TAGS if db.tags else 0))
+        if metrics:
+            engine.metrics(db)
         if filter is not None:
             engine.filter(db, filter)
+            if metrics:
+                engine.metrics_filter(db)
         out = db.fetch(ss=tags)
         return consensus_from_output(fb, out), _records_from_dump(raw, fb, out, strip=True)
-    return concat_consensus(run_ranges(engine, plan, plan_ranges(plan, batch_bases), mode, tags, filter=filter)), None
+    return concat_consensus(run_ranges(engine, plan, plan_ranges(plan, batch_bases), mode, tags, filter=filter, **mkw)), None
 
 
 def run_duplex(engine: Engine, raw: R.RawRecords, tags: bool = False, batch_bases: Optional[int] = None,
-               filter: Optional[FilterParams] = None) -> Consensus:
+               filter: Optional[FilterParams] = None, metrics: bool = False) -> Consensus:
     """callduplex alone (main.snake.py:155-164) on converted + extended records."""
     plan = plan_families(raw, "vote")
-    return concat_consensus(run_ranges(engine, plan, plan_ranges(plan, batch_bases), MODE_VOTE, tags, filter=filter))
+    mkw = {"metrics": True} if metrics else {}
+    return concat_consensus(run_ranges(engine, plan, plan_ranges(plan, batch_bases), MODE_VOTE, tags, filter=filter, **mkw))
 
 
 def molecular_records(raw: R.RawRecords) -> R.RawRecords:
@@ -583,14 +599,15 @@ def _run_names(tab, ids: np.ndarray, strands: np.ndarray):
 
 
 def run_molecular(engine: Engine, raw: R.RawRecords, tags: bool = False,
-                  min_consensus_base_quality: int = 0, filter: Optional[FilterParams] = None):
+                  min_consensus_base_quality: int = 0, filter: Optional[FilterParams] = None, metrics: bool = False):
     """fgbio CallMolecularConsensusReads with the step-1 flags (main.snake.py:54: pre 45, post 30,
     min-reads 1, min-consensus-base-quality 0, overlapping bases on) -> (Consensus over the runs,
     the run records).  Consensus family f is MI run f; its R1 / R2 are the single-strand consensus
     of the run's R1s / R2s.  The engine runs with min_consensus_base_quality for this call only.
-    filter: as run_step5's, with the molecular rules."""
+    filter, metrics: as run_step5's, with the molecular rules."""
     rm = molecular_records(raw)
     plan = plan_families(rm, "vote", family_order="mi-group")
     with engine.flags(min_consensus_base_quality=min_consensus_base_quality):
+        mkw = {"metrics": True} if metrics else {}
         return concat_consensus(run_ranges(engine, plan, plan_ranges(plan), MODE_VOTE, tags, filter=filter,
-                                           molecular=True)), rm
+                                           molecular=True, **mkw)), rm

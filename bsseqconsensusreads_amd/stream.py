@@ -56,7 +56,12 @@ class StreamJob:
     gpu_image: the chunks are decoded without unpacked bases (bam.StreamChunk.decode(packed=True)),
     their SEQ / QUAL bytes go up once a chunk and every batch's family images are made in HBM from
     them (Engine.image, bsdc_image_gather) instead of on the host: the same images, so the same
-    output files; an Engine stream only.  A split_ext chunk unpacks its bases on the host."""
+    output files; an Engine stream only.  A split_ext chunk unpacks its bases on the host.
+    metrics: the path of the run's metrics JSON (metrics.write): every batch, the
+    whole-chunk batches of a split_ext plan and the deferred templates' pass included, is reduced into
+    one accumulator on the engine's GPU (Engine.metrics; metrics_cycles rows of by_cycle) and the
+    file is written once at the end; the output files are those of the run without it.  An Engine
+    stream of one process only: not in a rank's stream, not with a runner."""
 
     in_bam: str
     fasta: Optional[str]
@@ -81,6 +86,8 @@ class StreamJob:
     late_splices: Optional[np.ndarray] = None
     first_key: Optional[tuple] = None
     regions: bool = False
+    metrics: Optional[str] = None
+    metrics_cycles: int = 512
     gpu_fastq: bool = False
     gpu_bam: bool = False
     gpu_image: bool = False
@@ -462,16 +469,18 @@ def step5_stream(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, p
                  chunk_bytes: int = bam.DEFAULT_CHUNK_BYTES, slack: int = bam.DEFAULT_SLACK,
                  batch_bases: Optional[int] = None, stats: Optional[dict] = None, gpu_bgzf: bool = False,
                  defer: Optional[int] = None, read_size: int = 8 << 20, filter=None, gpu_inflate: bool = False,
-                 gpu_fastq: bool = False, gpu_bam: bool = False, gpu_image: bool = False) -> dict:
+                 gpu_fastq: bool = False, gpu_bam: bool = False, gpu_image: bool = False,
+                 metrics: Optional[str] = None, metrics_cycles: int = 512) -> dict:
     """step5 in bounded memory, pipelined (run); defer: the span past which a template is
     deferred (default DEFAULT_DEFER_SPAN; 0 = off); read_size: compressed bytes per refill;
     filter: as step5's; gpu_inflate: the input's BGZF blocks inflate on the GPU (bgzf.GpuInflate);
     gpu_fastq: the FASTQ pair is formatted, checksummed and deflated on the GPU (StreamJob);
     gpu_bam: the BAM's records are written, checksummed and deflated on the GPU (StreamJob);
-    gpu_image: the family images are made on the GPU from the records' bytes (StreamJob)."""
+    gpu_image: the family images are made on the GPU from the records' bytes (StreamJob);
+    metrics: the run's consensus metrics, reduced on the GPU, written to this JSON file (StreamJob)."""
     job = StreamJob(in_bam, fasta, out_bam, fastq, prefix, threads, level, tags, gpu_bgzf, chunk_bytes, slack,
                     batch_bases, read_size, filter=filter, defer=defer, gpu_inflate=gpu_inflate, gpu_fastq=gpu_fastq,
-                    gpu_bam=gpu_bam, gpu_image=gpu_image)
+                    gpu_bam=gpu_bam, gpu_image=gpu_image, metrics=metrics, metrics_cycles=metrics_cycles)
     return _public(run(job, engine, stats=stats))
 
 
@@ -480,7 +489,7 @@ def molecular_stream(in_bam: str, out_bam: Optional[str], engine=None, prefix: O
                      chunk_bytes: int = bam.DEFAULT_CHUNK_BYTES, batch_bases: Optional[int] = None,
                      stats: Optional[dict] = None, gpu_bgzf: bool = False, min_consensus_base_quality: int = 0,
                      filter=None, gpu_inflate: bool = False, gpu_fastq: bool = False, gpu_bam: bool = False,
-                     gpu_image: bool = False) -> dict:
+                     gpu_image: bool = False, metrics: Optional[str] = None, metrics_cycles: int = 512) -> dict:
     """Rule call_consensus_reads_molecular (main.snake.py:46-55) in bounded memory: the same
     pipeline as step5_stream over a GroupReadsByUmi-ordered input cut between MI runs
     (stream_chunks(runs=True)); each chunk's runs are its consensus families (pipeline.molecular_records,
@@ -489,7 +498,8 @@ def molecular_stream(in_bam: str, out_bam: Optional[str], engine=None, prefix: O
     (main.snake.py:54, README.md:83); this holds about six chunks."""
     job = StreamJob(in_bam, None, out_bam, fastq, prefix, threads, level, tags, gpu_bgzf, chunk_bytes,
                     batch_bases=batch_bases, molecular=int(min_consensus_base_quality), filter=filter,
-                    gpu_inflate=gpu_inflate, gpu_fastq=gpu_fastq, gpu_bam=gpu_bam, gpu_image=gpu_image)
+                    gpu_inflate=gpu_inflate, gpu_fastq=gpu_fastq, gpu_bam=gpu_bam, gpu_image=gpu_image, metrics=metrics,
+                    metrics_cycles=metrics_cycles)
     return _public(run(job, engine, stats=stats))
 
 
@@ -641,9 +651,12 @@ def _run_chunk(eng, runner, ch: Chunk, mode: int, tags: bool, job: StreamJob, G:
             parts.append(pipeline.consensus_from_output(fb, runner.run_batch(fb, mode, tags, sub)))
         return pipeline.concat_consensus(parts)
     if ch.batches is None:  # (gpu_image: the whole-chunk path reads unpacked bases)
+        mkw = {} if job.metrics is None else {"metrics": True}
         return pipeline.run_step5(eng, R.unpack_bases(ch.raw), tags=tags, batch_bases=job.batch_bases,
-                                  filter=job.filter)[0]
+                                  filter=job.filter, **mkw)[0]
     fkw = {} if job.filter is None else {"filter": job.filter, "molecular": job.molecular is not None}
+    if job.metrics is not None:  # each batch is reduced into the engine's accumulator after its vote
+        fkw.update(metrics=True, molecular=job.molecular is not None)
     raw = ch.raw
     names = lambda fb: bam.family_names(fb.fam_mi, raw.mi_names, job.prefix)  # noqa: E731
     # an output formatted on the host reads the fetched bases: the BAM without gpu_bam, the pair without gpu_fastq
@@ -689,6 +702,10 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
                              "(no gpu_bgzf, gpu_inflate, gpu_fastq or gpu_bam)")
         if job.gpu_image:
             raise ValueError("a runner stream makes the family images on the host (no gpu_image)")
+    if job.metrics is not None and runner is not None:
+        raise ValueError("a runner stream reduces no metrics (no metrics: one process, one GPU)")
+    if job.metrics is not None and (job.rng is not None or job.owner is not None):
+        raise ValueError("metrics is not supported in a rank's stream yet (one process, one GPU)")
     if job.gpu_image and (job.rng is not None or job.owner is not None):
         raise ValueError("gpu_image is not supported in a rank's stream yet (one process, one GPU)")
     if job.gpu_fastq and job.fastq is None:
@@ -731,6 +748,8 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
     fault = Fault()
     inflater = None
     try:
+        if job.metrics is not None and late is None:  # (the deferred templates' pass adds into the same one)
+            eng.metrics_begin(job.metrics_cycles)
         if ref is not None:
             (runner if runner is not None else eng).load_reference(ref)
         if job.gpu_inflate:  # (called on the decoder thread, on its own HIP stream)
@@ -792,6 +811,11 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
                 if dspan else np.zeros((0, 2), np.int64)
             if solo and dspan:  # the deferred templates' pass and the assembly (or just the EOF blocks)
                 _finish_deferred(dataclasses.replace(job, prefix=prefix), eng, runner, back.marks, spill_path, info)
+            if job.metrics is not None and late is None:
+                from . import metrics as _metrics
+                _metrics.write(job.metrics, eng.metrics_fetch(), job.metrics_cycles,
+                               _metrics.run_params(eng.params, molecular, job.filter))
+                info["metrics"] = job.metrics
     finally:
         flags.__exit__(None, None, None)
         if own:

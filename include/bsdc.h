@@ -423,6 +423,63 @@ int32_t bsdc_image_gather_host(bsdc_ctx *ctx, const uint8_t *raw, int64_t n_raw,
                                int64_t n_rec, int64_t n_slots, uint8_t *seq_img, uint8_t *qual_img);
 const char *bsdc_image_last_error(void);
 
+/* (new exports, ABI 19 still) Per-run consensus metrics reduced on the device (no reference
+ * counterpart: a user of the reference histograms the tagged BAM's cD/aD/bD, cE/aE/bE and per-base
+ * tags with another tool before choosing FilterConsensusReads' thresholds; csrc/bsdc_metrics.hip,
+ * DESIGN.md sections 3.9 and 8.10).  The accumulator is bsdc_metrics_words(cycles) u64 words
+ * (BSDC_EINVAL for cycles outside 2..1024), zeroed once by the caller and added to by every call:
+ *   [0, 16)  counts: BSDC_METRICS_FAMILIES families seen, _EMITTED those with status & 1, _RECORDS the
+ *            output records measured (2 per emitted family that is not skipped), _SKIPPED emitted
+ *            families not read (a length beyond the stride, a wide row outside [0, n_wide)); from
+ *            bsdc_metrics_filter: _KEPT emitted families with filt == 0, _MINREADS / _READERR /
+ *            _NOCALL / _MEANQ emitted families carrying that reason bit, _MASKED the sum of masked;
+ *            the other words stay 0
+ *   BSDC_METRICS_DEPTH_HIST  [3][2][256]  [kind cD / aD / bD][end][min(D, 255)], one per record (an
+ *            absent b counts at 0)
+ *   BSDC_METRICS_RATE_HIST   [3][2][102]  [kind cE / aE / bE][end][bin], bin = min((int)floor((double)xE
+ *            * 1000.0), 100), an infinite rate 100, NaN 101 (an absent b counts at 0)
+ *   BSDC_METRICS_QUAL_HIST   [2][95]      [end][consensus quality, capped at 93] of every non-N column
+ *            inside the length; bin 94 = the N columns
+ *   BSDC_METRICS_BY_CYCLE    [2][cycles][6]  [end][min(column, cycles - 1)]: records covering the column,
+ *            no-calls, sum of consensus quality, sum of depth ad + bd, sum of strand errors ae + be,
+ *            disagreements (both rows present, both codes A/C/G/T, different)
+ * The views a / b, the rows' cut to the consensus length and the per-read values are bsdc_filter's
+ * (DESIGN.md 3.8).  bsdc_metrics reads `out` as the vote left it, so it is enqueued on the vote's
+ * stream after it and BEFORE bsdc_filter masks seq / qual: the histograms describe the unfiltered
+ * consensus.  n_wide = the rows of out->ss_wdepth / ss_werr (0 with none); molecular as bsdc_filter's
+ * kind.  bsdc_metrics_filter adds the filter's outcome, after bsdc_filter on the same stream.  Device
+ * pointers but for `out` itself; acc 8-byte aligned, the rows 4-byte aligned.  The *_host twins take
+ * host pointers and run the same per-record function sequentially on the CPU (no GPU needed; ctx
+ * may be NULL).  BSDC_EINVAL, before anything is enqueued, naming the field (bsdc_last_error of the
+ * context; bsdc_metrics_last_error, thread-local, also without one): a NULL buffer (ss_wide apart),
+ * cycles outside 2..1024, a stride that is no positive multiple of 16, a negative count, molecular
+ * outside 0..1. */
+#define BSDC_METRICS_FAMILIES 0
+#define BSDC_METRICS_EMITTED 1
+#define BSDC_METRICS_RECORDS 2
+#define BSDC_METRICS_SKIPPED 3
+#define BSDC_METRICS_KEPT 4
+#define BSDC_METRICS_MINREADS 5
+#define BSDC_METRICS_READERR 6
+#define BSDC_METRICS_NOCALL 7
+#define BSDC_METRICS_MEANQ 8
+#define BSDC_METRICS_MASKED 9
+#define BSDC_METRICS_DEPTH_HIST 16
+#define BSDC_METRICS_RATE_HIST (16 + 3 * 2 * 256)
+#define BSDC_METRICS_QUAL_HIST (BSDC_METRICS_RATE_HIST + 3 * 2 * 102)
+#define BSDC_METRICS_BY_CYCLE (BSDC_METRICS_QUAL_HIST + 2 * 95)
+
+int64_t bsdc_metrics_words(int32_t cycles);
+int32_t bsdc_metrics(bsdc_ctx *ctx, const bsdc_consensus *out, int64_t n_fam, int64_t n_wide, int32_t molecular,
+                     int32_t cycles, uint64_t *acc, void *stream);
+int32_t bsdc_metrics_filter(bsdc_ctx *ctx, const uint8_t *status, const uint8_t *filt, const uint16_t *masked,
+                            int64_t n_fam, uint64_t *acc, void *stream);
+int32_t bsdc_metrics_host(bsdc_ctx *ctx, const bsdc_consensus *out, int64_t n_fam, int64_t n_wide, int32_t molecular,
+                          int32_t cycles, uint64_t *acc);
+int32_t bsdc_metrics_filter_host(bsdc_ctx *ctx, const uint8_t *status, const uint8_t *filt, const uint16_t *masked,
+                                 int64_t n_fam, uint64_t *acc);
+const char *bsdc_metrics_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif
