@@ -39,6 +39,12 @@ class InflateBlockC(C.Structure):  # bsdc_inflate_block
  INFLATE_ESHORT, INFLATE_EINPUT, INFLATE_ECOUNTS, INFLATE_ENOEOB, INFLATE_ECODE, INFLATE_ERANGE) = range(1, 14)
 
 
+# bsdc_toolrec_rec as a numpy record: the tool-stage records' table (toolrec.tables)
+TOOLREC_REC = [("name_off", "<i8"), ("cig_off", "<i8"), ("aux_off", "<i8"), ("aux_len", "<i4"), ("n_cig", "<i4"),
+               ("ref_id", "<i4"), ("next_ref_id", "<i4"), ("next_pos", "<i4"), ("tlen", "<i4"), ("flag", "<u2"),
+               ("mapq", "u1"), ("name_len", "u1"), ("reserved", "<i4")]
+
+
 # bsdc_image_rec as a numpy record: the gather's table (batch.FamilyBatch.gather)
 IMAGE_REC = [("src", "<i8"), ("l_seq", "<i4"), ("skip", "<i4"), ("len", "<i4"), ("slot", "<u4")]
 
@@ -73,7 +79,9 @@ EXPORTS = ("bsdc_abi_version", "bsdc_ctx_create", "bsdc_ctx_set_params", "bsdc_c
            "bsdc_bgzf_inflate", "bsdc_bgzf_inflate_host", "bsdc_fastq_text_bound", "bsdc_fastq_tmp_bytes",
            "bsdc_fastq_format", "bsdc_bgzf_crc32", "bsdc_bam_bytes_bound", "bsdc_bam_tmp_bytes", "bsdc_bam_format",
            "bsdc_image_gather", "bsdc_image_gather_host", "bsdc_image_last_error", "bsdc_metrics_words", "bsdc_metrics",
-           "bsdc_metrics_filter", "bsdc_metrics_host", "bsdc_metrics_filter_host", "bsdc_metrics_last_error")
+           "bsdc_metrics_filter", "bsdc_metrics_host", "bsdc_metrics_filter_host", "bsdc_metrics_last_error",
+           "bsdc_toolrec_bytes_bound", "bsdc_toolrec_tmp_bytes", "bsdc_toolrec_format", "bsdc_toolrec_host",
+           "bsdc_toolrec_last_error")
 
 _lib = None
 
@@ -173,6 +181,19 @@ def load(path: str = LIB_PATH):
     lib.bsdc_metrics_filter_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.bsdc_metrics_filter_host.restype = C.c_int32
     lib.bsdc_metrics_last_error.restype = C.c_char_p
+    lib.bsdc_toolrec_bytes_bound.argtypes = [C.c_int64] * 5
+    lib.bsdc_toolrec_bytes_bound.restype = C.c_int64
+    lib.bsdc_toolrec_tmp_bytes.argtypes = [C.c_int64]
+    lib.bsdc_toolrec_tmp_bytes.restype = C.c_int64
+    lib.bsdc_toolrec_format.argtypes = [C.POINTER(ConsensusC), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.bsdc_toolrec_format.restype = C.c_int32
+    lib.bsdc_toolrec_host.argtypes = [C.POINTER(ConsensusC), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_int64]
+    lib.bsdc_toolrec_host.restype = C.c_int32
+    lib.bsdc_toolrec_last_error.restype = C.c_char_p
     if lib.bsdc_abi_version() != BSDC_ABI_VERSION:
         raise RuntimeError("libbsdc ABI %d != %d" % (lib.bsdc_abi_version(), BSDC_ABI_VERSION))
     if path == LIB_PATH:

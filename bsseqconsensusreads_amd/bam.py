@@ -1014,7 +1014,7 @@ def duplex_records(cons, raw: R.RawRecords, prefix: str, threads: int = 0, molec
 
 
 def consensus_sharded(eng, raw: R.RawRecords, tags: bool, batch_bases: Optional[int] = None, dist=None,
-                      filter=None, metrics: bool = False):
+                      filter=None, metrics: bool = False, toolrec: Optional[str] = None):
     """pipeline.run_step5 over the ranks of `dist` (None = this process alone): every rank forms
     the same family plan, runs the batches shard.deal gives it on its own GPU, and rank 0 gets the
     consensus of all batches in plan order (shard.gather_in_order; other ranks get None).  A plan
@@ -1023,9 +1023,13 @@ def consensus_sharded(eng, raw: R.RawRecords, tags: bool, batch_bases: Optional[
     from . import pipeline, shard
     if dist is None or dist.get_world_size() == 1:
         mkw = {"metrics": True} if metrics else {}
+        if toolrec is not None:
+            mkw["toolrec"] = toolrec
         return pipeline.run_step5(eng, raw, tags=tags, batch_bases=batch_bases, filter=filter, **mkw)[0]
     if filter is not None:
         raise ValueError("the consensus filter is not supported with several ranks yet")
+    if toolrec is not None:
+        raise ValueError("the group-sorted BAM of the tool-stage records is not supported with several ranks yet")
     if metrics:
         raise ValueError("metrics is not supported with several ranks yet")
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -1042,7 +1046,8 @@ def consensus_sharded(eng, raw: R.RawRecords, tags: bool, batch_bases: Optional[
 
 def step5(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, prefix: Optional[str] = None, threads: int = 0,
           level: int = 6, fastq: Optional[Tuple[str, str]] = None, tags: bool = True, batch_bases: Optional[int] = None,
-          dist=None, filter=None, metrics: Optional[str] = None, metrics_cycles: int = 512) -> dict:
+          dist=None, filter=None, metrics: Optional[str] = None, metrics_cycles: int = 512,
+          groupsort_bam: Optional[str] = None) -> dict:
     """Rules convert_Bstrain .. callduplex (main.snake.py:121-164) as one call on files; with
     `fastq`, also the following consensusduplex_to_fq rule (main.snake.py:167-177) straight from
     the consensus records (out_bam may then be None: no BAM round trip).  The stream runs as
@@ -1050,7 +1055,10 @@ def step5(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, prefix: 
     are shared by the ranks (one GPU each) and rank 0 writes the files.  filter (filter.FilterParams):
     fgbio FilterConsensusReads on the device between the vote and the records -- the outputs hold
     the kept templates, masked, and the info dict a `filter` entry (filter.summary).  metrics: the
-    path of the run's metrics JSON, reduced on the device from every batch (one rank)."""
+    path of the run's metrics JSON, reduced on the device from every batch (one rank).
+    groupsort_bam: the path of a BAM of the records after tool 1 and tool 2 in TemplateCoordinate
+    order (rule groupsort_convert's file, main.snake.py:144-153), encoded by the host
+    twin (bsdc_toolrec_host) from every batch's stage dump; one rank."""
     from .device import Engine
     header, raw = read_bam(in_bam, threads)
     ref = read_fasta(fasta, header)
@@ -1061,6 +1069,8 @@ def step5(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, prefix: 
         if metrics is not None:
             eng.metrics_begin(metrics_cycles)
         mkw = {"metrics": True} if metrics is not None else {}
+        if groupsort_bam is not None:
+            mkw["toolrec"] = "host"
         cons = consensus_sharded(eng, raw, tags and out_bam is not None, batch_bases, dist, filter, **mkw)
         if metrics is not None:
             _write_metrics(eng, metrics, metrics_cycles, False, filter)
@@ -1069,7 +1079,26 @@ def step5(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, prefix: 
             eng.close()
     if cons is None:  # not rank 0
         return {"records_in": raw.n}
-    return _write_consensus(cons, raw, raw.n, header, prefix, out_bam, fastq, level, threads, False, filter)
+    info = _write_consensus(cons, raw, raw.n, header, prefix, out_bam, fastq, level, threads, False, filter)
+    if groupsort_bam is not None:
+        info["groupsort_bam"] = _write_groupsort(groupsort_bam, header, cons.toolrec, level, threads)
+    return info
+
+
+def _write_groupsort(path: str, header: BamHeader, pieces, level: int, threads: int) -> dict:
+    """The batches' tool-stage records (pipeline.ToolrecPiece of host bytes, in order) as the
+    group-sorted BAM through the ordinary host writer -> the info entry."""
+    from . import bgzf, toolrec
+    w = bgzf.BamWriter(path, toolrec.header(header), level)
+    n = raw_bytes = 0
+    try:
+        for x in pieces:
+            w.add_raw(x.host(0, x.fams), threads)
+            n += x.n_rec
+            raw_bytes += int(x.foff[-1])
+    finally:
+        w.close(threads)
+    return {"records": n, "raw_bytes": raw_bytes, "compressed_bytes": os.path.getsize(path)}
 
 
 def _write_metrics(eng, path: str, cycles: int, molecular: bool, flt):

@@ -11,6 +11,10 @@ Both take fgbio FilterConsensusReads' options as --filter-* (DESIGN.md 3.8): wit
 OUT.bam and the FASTQ pair hold the kept, masked templates (rule consensus_to_fq's input,
 main.snake.py:70-80, with no FilterConsensusReads run; --gpus 1 only).
 
+step5 --groupsort-bam PATH also writes the records after tool 1 and tool 2 in TemplateCoordinate
+order: the file rule groupsort_convert leaves (main.snake.py:144-153), the input of fgbio
+CallDuplexConsensusReads at :163 (--gpus 1 only).
+
 OUT.bam may be '-' to skip the BAM when only the FASTQ pair is wanted.  Errors exit non-zero with
 the message on stderr, so Snakemake aborts the rule and removes partial outputs, as it does for
 the reference tools (tools/2.extend_gap.py:179-180 raises on a record without MI).
@@ -75,6 +79,12 @@ def parse(argv):
                             "same output files)")
         p.add_argument("--metrics-cycles", type=int, default=512, metavar="N",
                        help="rows of the per-cycle table, 2..1024; columns at and past N - 1 share the last row")
+        # (registered for both commands: molecular refuses it with the reason, below)
+        p.add_argument("--groupsort-bam", default=None, metavar="PATH",
+                       help="also write the records after tool 1 and tool 2, in fgbio TemplateCoordinate order, as "
+                            "the BAM rule groupsort_convert leaves (the input of fgbio CallDuplexConsensusReads): "
+                            "encoded on the GPU from the stage dump, unfiltered whatever --filter-* says (--gpus 1; "
+                            "the same output files)")
         p.add_argument("--batch-bases", type=int, default=None, help="device batch budget in bases")
         p.add_argument("--chunk-mb", type=int, default=64, help="--stream: record MiB per chunk")
         if name == "step5":
@@ -124,6 +134,11 @@ def parse(argv):
         ap.error("--fastq1 and --fastq2 go together")
     if a.output == "-" and a.fastq1 is None:
         ap.error("nothing to write: give OUT.bam or --fastq1/--fastq2")
+    if a.groupsort_bam is not None and a.cmd != "step5":
+        ap.error("--groupsort-bam applies to step5 only: %s (step 1) runs no tools, so there are no tool-stage "
+                 "records to write" % a.cmd)
+    if a.groupsort_bam is not None and a.gpus > 1:
+        ap.error("--groupsort-bam is not supported with --gpus %d yet (one process, one GPU)" % a.gpus)
     if a.metrics is not None and getattr(a, "gpus", 1) > 1:
         ap.error("--metrics is not supported with --gpus %d yet (one process, one GPU)" % a.gpus)
     if not 2 <= a.metrics_cycles <= 1024:
@@ -251,7 +266,8 @@ def main(argv=None) -> int:
                                         batch_bases=a.batch_bases, gpu_bgzf=a.gpu_bgzf == "true", filter=flt,
                                         gpu_inflate=a.gpu_inflate == "true", gpu_fastq=a.gpu_fastq == "true",
                                         gpu_bam=a.gpu_bam == "true", gpu_image=a.gpu_image == "true",
-                                        metrics=a.metrics, metrics_cycles=a.metrics_cycles)
+                                        metrics=a.metrics, metrics_cycles=a.metrics_cycles,
+                                        **({"groupsort_bam": a.groupsort_bam} if a.groupsort_bam else {}))
             elif a.cmd == "step5" and a.gpu_image == "true":
                 raise ValueError("--gpu-image applies to the streaming step only: %s is not coordinate-sorted "
                                  "and would be read whole" % a.input)
@@ -264,7 +280,8 @@ def main(argv=None) -> int:
             elif a.cmd == "step5":
                 info = bam.step5(a.input, a.reference, out, eng, a.read_name_prefix, a.threads, a.compression, fq,
                                  tags=a.output_per_base_tags == "true", batch_bases=a.batch_bases, dist=dist,
-                                 filter=flt, metrics=a.metrics, metrics_cycles=a.metrics_cycles)
+                                 filter=flt, metrics=a.metrics, metrics_cycles=a.metrics_cycles,
+                                 **({"groupsort_bam": a.groupsort_bam} if a.groupsort_bam else {}))
             elif a.stream == "true":
                 info = bam.molecular_stream(a.input, out, eng, a.read_name_prefix, a.threads, a.compression, fq,
                                             tags=a.output_per_base_tags == "true", chunk_bytes=a.chunk_mb << 20,

@@ -81,6 +81,21 @@ class BamText:
     event: "torch.cuda.Event"
 
 
+@dataclass
+class ToolrecText:
+    """What Engine.toolrec leaves on a DeviceBatch: the BAM records of the batch's records after tool
+    1 and tool 2 in HBM (bsdc_toolrec_format).  rec: the bytes (uint8, `cap` of them allocated); off:
+    int64 [n_rec + 1] on the device, the records' byte offsets, off[n_rec] = their size; foff: int64
+    [F + 1] on the device, off at each family's first record (and the size); event: recorded after
+    the launch.  Dropping the object releases the records."""
+
+    rec: torch.Tensor
+    off: torch.Tensor
+    foff: torch.Tensor
+    cap: int
+    event: "torch.cuda.Event"
+
+
 class DeviceBatch:
     """A FamilyBatch resident in HBM plus its output buffers."""
 
@@ -138,6 +153,7 @@ class DeviceBatch:
                 self.ss_werr = torch.zeros(nw, dtype=torch.int16, device=device)
         self.fastq: Optional[FastqText] = None  # Engine.fastq
         self.bamrec: Optional[BamText] = None  # Engine.bam_records
+        self.toolrec: Optional[ToolrecText] = None  # Engine.toolrec
         self.filt = self.masked = None
         if filt:  # bsdc_filter's outputs: reason bits per family, newly masked columns per end
             self.filt = torch.zeros(max(F, 1), dtype=torch.uint8, device=device)
@@ -189,8 +205,9 @@ class DeviceBatch:
         return (self.status[:F].cpu().numpy(),
                 self.len[:2 * F].cpu().numpy().view(np.uint16).astype(np.int32).reshape(F, 2))
 
-    def fetch(self, alloc=None, ss: bool = True, seqqual: bool = True):
-        """-> dict of numpy arrays (consensus and, if dumped, the post-tool records; after
+    def fetch(self, alloc=None, ss: bool = True, seqqual: bool = True, dump: bool = True):
+        """dump=False leaves the stage dump of a dump batch in HBM (Engine.toolrec read it there).
+        -> dict of numpy arrays (consensus and, if dumped, the post-tool records; after
         Engine.filter also "filt" [F] and "masked" [F, 2]).  ss=False leaves the single-strand rows
         of a tags batch in HBM (a filtered output without consensus tags, or one whose records
         Engine.bam_records wrote there).  seqqual=False (after Engine.fastq or Engine.bam_records,
@@ -221,7 +238,8 @@ class DeviceBatch:
             if self.n_wide:
                 t.update(ss_wdepth=self.ss_wdepth, ss_werr=self.ss_werr)
         Rn = self.n_rec
-        if self.dump:
+        dump = dump and self.dump
+        if dump:
             t.update(dump_pos=self.dump_pos[:Rn], dump_len=self.dump_len[:Rn], dump_tags=self.dump_tags[:Rn],
                      dump_seq=self.dump_seq, dump_qual=self.dump_qual)
         if alloc is None:
@@ -263,7 +281,7 @@ class DeviceBatch:
                 np.zeros((0, 4, self.stride), np.uint16)
             out["ss_werr"] = a["ss_werr"].view(np.uint16).reshape(W, 4, self.stride) if W else \
                 np.zeros((0, 4, self.stride), np.uint16)
-        if self.dump:
+        if dump:
             out["dump_pos"] = a["dump_pos"]
             out["dump_len"] = a["dump_len"].view(np.uint16).astype(np.int32)
             out["dump_tags"] = a["dump_tags"]
@@ -586,6 +604,44 @@ class Engine:
             ev.record(s)
         db.bamrec = BamText(rec, off, cap, ev)
         return db.bamrec
+
+    def toolrec(self, db: DeviceBatch, tables, stream: Optional[torch.cuda.Stream] = None) -> ToolrecText:
+        """The batch's records after tool 1 and tool 2 written as BAM records where the stage dump
+        lies (bsdc_toolrec_format), enqueued on the stream that ran bsdc_run(.. | MODE_DUMP), after
+        it.  tables: toolrec.Tables of the batch's records (toolrec.batch_tables).  The tables go up,
+        a buffer of the size known beforehand (bsdc_toolrec_bytes_bound) is allocated, and db.toolrec
+        holds it with an event recorded behind the launch."""
+        if not db.dump:
+            raise ValueError("toolrec: the batch was uploaded without dump=True")
+        if tables.n != db.n_rec:
+            raise ValueError("toolrec: %d table entries for %d records" % (tables.n, db.n_rec))
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        n = db.n_rec
+        n_dump = int(db.dump_seq.numel()) // 4 * 4
+        if n_dump < db.n_slots:  # (every record's slot lies inside the batch's n_slots)
+            raise ValueError("toolrec: the dump buffers hold %d bytes, the batch's slots %d" % (n_dump, db.n_slots))
+        cap = tables.bound(n_dump)
+        tab_h = np.ascontiguousarray(tables.tab) if n else np.zeros(1, _lib.TOOLREC_REC)
+        fam_first = np.ascontiguousarray(db.fb.fam_off if db.fb is not None else [0, n], np.int64)
+        with torch.cuda.device(self.device), torch.cuda.stream(s):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8)).to(self.device)  # noqa: E731
+            d_tab, d_names, d_cig, d_aux = up(tab_h), up(tables.names), up(tables.cigar), up(tables.aux)
+            rec = torch.empty(max(cap, 16), dtype=torch.uint8, device=self.device)
+            off = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+            tmp = torch.empty(int(self.lib.bsdc_toolrec_tmp_bytes(n)), dtype=torch.uint8, device=self.device)
+            p = lambda t: C.c_void_p(_dptr(t))  # noqa: E731
+            rc = self.lib.bsdc_toolrec_format(C.byref(db._o), p(db.t["rec"]), n, n_dump, p(d_tab),
+                                              C.c_void_p(tab_h.ctypes.data), p(d_names), int(tables.names.shape[0]),
+                                              p(d_cig), int(tables.cigar.shape[0]), p(d_aux), int(tables.aux.shape[0]),
+                                              p(off), p(rec), cap, p(tmp), C.c_void_p(s.cuda_stream))
+            if rc != 0:
+                raise RuntimeError("bsdc_toolrec_format failed (%d): %s" % (
+                    rc, self.lib.bsdc_toolrec_last_error().decode()))
+            foff = off[torch.from_numpy(fam_first).to(self.device)]
+            ev = torch.cuda.Event()
+            ev.record(s)
+        db.toolrec = ToolrecText(rec, off, foff, cap, ev)
+        return db.toolrec
 
     def tables(self):
         lr = np.zeros(256, np.int64)

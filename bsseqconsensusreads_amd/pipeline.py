@@ -88,6 +88,32 @@ class Consensus:
     # with run_batches(bam_tables=...): one BamPiece per batch, the kept families' BAM records in
     # HBM (Engine.bam_records); the ss rows then stayed on the device (ss is None)
     bamrec: Optional[list] = None
+    # with run_batches(toolrec=...): one ToolrecPiece per batch, the BAM records of the batch's
+    # records after tool 1 and tool 2 (cli step5 --groupsort-bam)
+    toolrec: Optional[list] = None
+
+
+@dataclass
+class ToolrecPiece:
+    """One batch's records after tool 1 and tool 2 as BAM records and where its families lie in them:
+    rec = the uint8 device tensor (event = recorded behind the launch) or, from the host twin, a
+    numpy array (event None); fams = the batch's families, every one of them, n_rec their records;
+    foff int64 [fams + 1] = the byte offset of each family's first record, the last one = the
+    records' size (checked against the buffer).  Dropping it releases the records."""
+
+    rec: object
+    event: object
+    fams: int
+    n_rec: int
+    foff: np.ndarray
+
+    def ranges(self, a: int, b: int) -> list:
+        """families a..b-1 as bgzf.GpuBgzf.submit_device's pieces of the one file (device records)."""
+        return [(self.rec, int(self.foff[a]), int(self.foff[b]), self.event)]
+
+    def host(self, a: int, b: int) -> bytes:
+        """families a..b-1 of host records as bytes"""
+        return self.rec[int(self.foff[a]):int(self.foff[b])].tobytes()
 
 
 @dataclass
@@ -301,10 +327,10 @@ def plan_ranges(plan: FamilyPlan, batch_bases: Optional[int] = None):
 
 def run_ranges(engine: Engine, plan: FamilyPlan, ranges, mode: int, tags: bool = False,
                timing: Optional[dict] = None, filter: Optional[FilterParams] = None,
-               molecular: bool = False, metrics: bool = False) -> List[Consensus]:
+               molecular: bool = False, metrics: bool = False, toolrec=None, toolrec_host: bool = False) -> List[Consensus]:
     """Plan family ranges through the kernels (run_batches), each materialized into the engine's
     staging images just before it uploads: the host builds range i + 1 while the kernels of range
-    i run.  `timing` also gets the seconds of materialize.  metrics: run_batches'."""
+    i run.  `timing` also gets the seconds of materialize.  metrics, toolrec, toolrec_host: run_batches'."""
     import time
     T = timing if timing is not None else {}
 
@@ -315,6 +341,8 @@ def run_ranges(engine: Engine, plan: FamilyPlan, ranges, mode: int, tags: bool =
             T["materialize"] = T.get("materialize", 0.0) + time.perf_counter() - t0
             yield fb
     mkw = {"metrics": True} if metrics else {}
+    if toolrec is not None:
+        mkw.update(toolrec=toolrec, toolrec_host=toolrec_host)
     return run_batches(engine, staged(), mode, tags, T, filter, molecular, **mkw)
 
 
@@ -329,7 +357,8 @@ def materialize_ranges(plan: FamilyPlan, ranges, images=None, gather: bool = Fal
 def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
                 timing: Optional[dict] = None, filter: Optional[FilterParams] = None,
                 molecular: bool = False, fastq_names=None, seqqual: bool = True, bam_tables=None,
-                bam_tags: bool = True, raw_bases: Optional[np.ndarray] = None, metrics: bool = False) -> List[Consensus]:
+                bam_tags: bool = True, raw_bases: Optional[np.ndarray] = None, metrics: bool = False,
+                toolrec=None, toolrec_host: bool = False) -> List[Consensus]:
     """Materialized batches (any iterable, taken one at a time) through the kernels, one launch
     each, output per batch in order; a batch uploads and launches before the one before it is
     fetched.  `timing`: seconds added per host step (upload, fetch = wait + copy out, unpack).
@@ -348,9 +377,16 @@ def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
     `metrics`: each batch is reduced into the engine's metrics accumulator (Engine.metrics_begin)
     right after its vote, before a filter masks it, and the filter's outcome is added after it
     (Engine.metrics, Engine.metrics_filter); like a filter it needs the tags' rows in
-    HBM, which are copied out only with `tags`."""
+    HBM, which are copied out only with `tags`.
+    `toolrec` (batch -> toolrec.Tables of its records): each batch runs with BSDC_MODE_DUMP and its
+    records after tool 1 and tool 2 are written as BAM records on the device right after the launch
+    (Engine.toolrec; the dump stays in HBM) -- or, with toolrec_host, by the host twin from the
+    fetched dump -- and its Consensus carries them (Consensus.toolrec); whatever a filter drops, they
+    are the unfiltered input side."""
     import time
     T = timing if timing is not None else {}
+    if toolrec is not None:
+        mode |= MODE_DUMP
     parts: List[Consensus] = []
     prev = None
     raw_dev = None
@@ -358,17 +394,21 @@ def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
     def out(fb, db):
         t0 = time.perf_counter()
         if seqqual or (db.fastq is None and db.bamrec is None):
-            o = db.fetch(ss=tags and db.bamrec is None)
+            o = db.fetch(ss=tags and db.bamrec is None, dump=toolrec_host)
         else:
-            o = db.fetch(seqqual=False)
+            o = db.fetch(seqqual=False, dump=toolrec_host)  # (the small fetch copies no dump either way)
         t1 = time.perf_counter()
         parts.append(consensus_from_output(fb, o))
         if db.fastq is not None:
             parts[-1].fastq = [_fastq_piece(db, parts[-1])]
         if db.bamrec is not None:
             parts[-1].bamrec = [_bam_piece(db, parts[-1], o["bam_off"])]
+        if toolrec is not None:
+            parts[-1].toolrec = [_toolrec_piece(db, fb, o, tables[id(db)] if toolrec_host else None)]
+            tables.pop(id(db), None)
         T["fetch"] = T.get("fetch", 0.0) + t1 - t0
         T["unpack"] = T.get("unpack", 0.0) + time.perf_counter() - t1
+    tables = {}  # (toolrec_host: the batches' tables until their dump is fetched)
     for fb in batches:
         t0 = time.perf_counter()
         if fb.gather is not None and raw_dev is None:
@@ -376,8 +416,12 @@ def run_batches(engine: Engine, batches, mode: int, tags: bool = False,
                 raise ValueError("batches without host images need raw_bases (the records' SEQ / QUAL bytes)")
             raw_dev = engine.upload_raw(raw_bases)
         db = engine.upload(fb, tags=tags or metrics or (bam_tables is not None and bam_tags), filt=filter is not None,
-                           raw_dev=raw_dev)
+                           raw_dev=raw_dev, **({"dump": True} if toolrec is not None else {}))
         engine.run(db, mode | (MODE_TAGS if db.tags else 0))
+        if toolrec is not None and toolrec_host:
+            tables[id(db)] = toolrec(fb)
+        elif toolrec is not None:
+            engine.toolrec(db, toolrec(fb))
         if metrics:
             engine.metrics(db, molecular)
         if filter is not None:
@@ -415,6 +459,23 @@ def _fastq_piece(db, cons: Consensus) -> FastqPiece:
     return FastqPiece(fq.text, fq.event, int(k.shape[0]), koff)
 
 
+def _toolrec_piece(db, fb, out: dict, tables) -> ToolrecPiece:
+    """The batch's tool-stage records as a ToolrecPiece: the device's (Engine.toolrec; the families'
+    offsets fetched, the total checked against the buffer; a stream synchronised by the fetch
+    before) or, with `tables`, the host twin's from the fetched dump."""
+    if tables is not None:
+        from . import toolrec as _toolrec
+        off, buf = _toolrec.host(tables, fb.rec_off, out["dump_pos"], out["dump_len"], out["dump_tags"],
+                                 out["dump_seq"], out["dump_qual"])
+        foff = off[np.asarray(fb.fam_off, np.int64)]
+        return ToolrecPiece(buf[:int(off[-1])], None, fb.n_fam, fb.n_rec, foff)
+    t = db.toolrec
+    foff = t.foff.cpu().numpy().astype(np.int64)
+    if not 0 <= int(foff[-1]) <= t.cap or (np.diff(foff) < 0).any():
+        raise RuntimeError("tool-stage records: the device wrote %d bytes (buffer %d)" % (int(foff[-1]), t.cap))
+    return ToolrecPiece(t.rec, t.event, fb.n_fam, fb.n_rec, foff)
+
+
 def _bam_piece(db, cons: Consensus, off: np.ndarray) -> BamPiece:
     """The batch's device records as a BamPiece: the fetched offsets at the kept families, the
     device's total checked against the buffer (a stream synchronised by the fetch before)."""
@@ -435,6 +496,7 @@ def concat_consensus(parts: List[Consensus]) -> Consensus:
         return parts[0]
     fastq = [x for p in parts for x in p.fastq] if parts and all(p.fastq is not None for p in parts) else None
     bamrec = [x for p in parts for x in p.bamrec] if parts and all(p.bamrec is not None for p in parts) else None
+    toolrec = [x for p in parts for x in p.toolrec] if parts and all(p.toolrec is not None for p in parts) else None
     if not parts:
         z = np.zeros(0, np.int32)
         return Consensus(z, np.zeros(0, np.uint8), np.zeros((0, 2), np.int32), np.zeros((0, 2, 16), np.uint8),
@@ -469,18 +531,28 @@ def concat_consensus(parts: List[Consensus]) -> Consensus:
     return Consensus(np.concatenate([p.fam_mi for p in parts]), np.concatenate([p.status for p in parts]),
                      np.concatenate([p.length for p in parts]), np.concatenate([pad(p.seq) for p in parts]),
                      np.concatenate([pad(p.qual) for p in parts]), fro.astype(np.int64),
-                     np.concatenate([np.asarray(p.fam_src, np.int64) for p in parts]), ss, filt, masked, fastq, bamrec)
+                     np.concatenate([np.asarray(p.fam_src, np.int64) for p in parts]), ss, filt, masked, fastq, bamrec,
+                     toolrec)
 
 
-def _tools_batched(engine: Engine, raw: R.RawRecords, batch_bases: Optional[int]) -> OutRecords:
-    """Tools 1 + 2 over tool-2 MI groups, batch by batch, as tool-2 output records in order."""
+def _tools_batched(engine: Engine, raw: R.RawRecords, batch_bases: Optional[int],
+                   recbytes: Optional[dict] = None) -> OutRecords:
+    """Tools 1 + 2 over tool-2 MI groups, batch by batch, as tool-2 output records in order.
+    recbytes: a dict that receives every record's BAM record bytes (toolrec.host), by input record."""
     plan = plan_families(raw, "full", engine.ref, family_order="mi-group")
     parts = []
     for a, b in plan_ranges(plan, batch_bases):
         fb = materialize(plan, a, b)
         db = engine.upload(fb, dump=True)
         engine.run(db, MODE_CONVERT | MODE_EXTEND | MODE_DUMP)
-        parts.append(_records_from_dump(raw, fb, db.fetch(), strip=True))
+        out = db.fetch()
+        parts.append(_records_from_dump(raw, fb, out, strip=True))
+        if recbytes is not None:
+            from . import toolrec as _toolrec
+            off, buf = _toolrec.host(_toolrec.batch_tables(raw, fb), fb.rec_off, out["dump_pos"], out["dump_len"],
+                                     out["dump_tags"], out["dump_seq"], out["dump_qual"])
+            for r, k in enumerate(fb.src):
+                recbytes[int(k)] = buf[int(off[r]):int(off[r + 1])]
     return _cat_records(parts)
 
 
@@ -506,21 +578,33 @@ def _cat_records(parts: List[OutRecords]) -> OutRecords:
 
 
 def run_step5(engine: Engine, raw: R.RawRecords, dump: bool = False, tags: bool = False,
-              batch_bases: Optional[int] = None, filter: Optional[FilterParams] = None, metrics: bool = False):
+              batch_bases: Optional[int] = None, filter: Optional[FilterParams] = None, metrics: bool = False,
+              toolrec: Optional[str] = None):
     """Rules convert_Bstrain .. callduplex (main.snake.py:121-164) -> (Consensus, tool-2 records or None).
     tags: also the single-strand reads and column statistics of fgbio's consensus tags (Consensus.ss).
     batch_bases: device batch budget (DEFAULT_BATCH_BASES); dump (the tool-2 records, parity
     tests) needs the stream in one batch.  filter: fgbio FilterConsensusReads on the device after
     the vote (Consensus.filt / masked; seq and qual come back masked).  metrics: every batch adds
-    into the engine's metrics accumulator (run_batches' `metrics`; Engine.metrics_begin first)."""
+    into the engine's metrics accumulator (run_batches' `metrics`; Engine.metrics_begin first).
+    toolrec: "device" / "host" -- the Consensus also carries the records after tool 1 and tool 2 as
+    BAM records (Consensus.toolrec; run_batches' `toolrec`, written on the device or by the host
+    twin; a split_ext plan's come from the twin either way)."""
     plan = plan_families(raw, "full", engine.ref)
     mkw = {"metrics": True} if metrics else {}
     if plan.split_ext:
         # a TemplateCoordinate family lacks a record's tool-2 extension partner: run the tools as
         # their own launches (tool-2 MI groups), then callduplex on their records
-        t2 = _tools_batched(engine, raw, batch_bases)
+        rb = {} if toolrec is not None else None
+        t2 = _tools_batched(engine, raw, batch_bases, rb)
         cons = run_duplex(engine, raw_from_records(raw, t2), tags, batch_bases, filter, **mkw)
         cons.fam_src = t2.src[cons.fam_src]  # raw2 record k is tool-2 record k
+        if rb is not None:  # the families' records in the vote's order
+            recs = [rb[int(k)] for k in cons.fam_src]
+            off = np.zeros(len(recs) + 1, np.int64)
+            off[1:] = np.cumsum([x.shape[0] for x in recs])
+            buf = np.concatenate(recs) if recs else np.zeros(0, np.uint8)
+            cons.toolrec = [ToolrecPiece(buf, None, int(cons.status.shape[0]), len(recs),
+                                         off[np.asarray(cons.fam_rec_off, np.int64)])]
         return cons, (t2 if dump else None)
     mode = MODE_CONVERT | MODE_EXTEND | MODE_VOTE
     if dump:
@@ -535,7 +619,13 @@ def run_step5(engine: Engine, raw: R.RawRecords, dump: bool = False, tags: bool 
                 engine.metrics_filter(db)
         out = db.fetch(ss=tags)
         return consensus_from_output(fb, out), _records_from_dump(raw, fb, out, strip=True)
-    return concat_consensus(run_ranges(engine, plan, plan_ranges(plan, batch_bases), mode, tags, filter=filter, **mkw)), None
+    if toolrec is not None:
+        from . import toolrec as _toolrec
+        mkw.update(toolrec=lambda fb: _toolrec.batch_tables(raw, fb), toolrec_host=toolrec == "host")
+    cons = concat_consensus(run_ranges(engine, plan, plan_ranges(plan, batch_bases), mode, tags, filter=filter, **mkw))
+    if toolrec is not None and cons.toolrec is None:  # (no batch at all)
+        cons.toolrec = []
+    return cons, None
 
 
 def run_duplex(engine: Engine, raw: R.RawRecords, tags: bool = False, batch_bases: Optional[int] = None,

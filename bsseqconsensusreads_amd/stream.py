@@ -61,7 +61,13 @@ class StreamJob:
     whole-chunk batches of a split_ext plan and the deferred templates' pass included, is reduced into
     one accumulator on the engine's GPU (Engine.metrics; metrics_cycles rows of by_cycle) and the
     file is written once at the end; the output files are those of the run without it.  An Engine
-    stream of one process only: not in a rank's stream, not with a runner."""
+    stream of one process only: not in a rank's stream, not with a runner.
+    groupsort_bam: the path of a BAM of the records after tool 1 and tool 2 in TemplateCoordinate
+    order (rule groupsort_convert's file): every batch runs with BSDC_MODE_DUMP and
+    its records are written in HBM (Engine.toolrec), checksummed and deflated there through a second
+    BamWriter (add_device); a split_ext chunk's come from the host twin.  The file is cut at the
+    deferred keys as the other outputs are.  Step 5, an Engine stream of one process only; the other
+    output files are those of the run without it."""
 
     in_bam: str
     fasta: Optional[str]
@@ -88,6 +94,7 @@ class StreamJob:
     regions: bool = False
     metrics: Optional[str] = None
     metrics_cycles: int = 512
+    groupsort_bam: Optional[str] = None
     gpu_fastq: bool = False
     gpu_bam: bool = False
     gpu_image: bool = False
@@ -341,26 +348,33 @@ class BackEnd(_Stages):
     bam_device (a call that gives the device): likewise the BAM takes a chunk's records from HBM
     where its Consensus carries them (Consensus.bamrec, pipeline.BamPiece; BamWriter.add_device):
     no tagged records are built for such a chunk (untagged ones only when the FASTQ pair is
-    formatted on the host); bam_counters: the BAM's GpuBgzf counters at the close."""
+    formatted on the host); bam_counters: the BAM's GpuBgzf counters at the close.
+    groupsort ((path, a call that gives the device)): a second BamWriter for the tool-stage
+    records (Consensus.toolrec, pipeline.ToolrecPiece), whose whole blocks are
+    checksummed and deflated on the GPU as bam_device's are; put()'s gcuts give its cuts as family
+    indices (it holds every family, kept or not), and a mark's fourth offset is its length there."""
 
     def __init__(self, fault: Fault, out_bam: Optional[str], fastq, header, prefix: str, threads: int, level: int,
                  bufs: "bam.BufferPool", molecular: bool = False, gz_device=None, fragment: Optional[str] = None,
                  marks: Optional[list] = None, first_key=(MINKEY, 0, 1), tie: int = 1, on_written=None,
-                 fq_device=None, bam_device=None):
+                 fq_device=None, bam_device=None, groupsort=None):
         self.fault, self.out_bam, self.fastq, self.header, self.prefix = fault, out_bam, fastq, header, prefix
         self.threads, self.level, self.bufs, self.molecular, self.gz_device = threads, level, bufs, molecular, gz_device
         self.fragment, self.first_key, self.tie, self.on_written = fragment, first_key, tie, on_written
         self.marks = [] if marks is None else marks
         self.fq_device, self.fastq_counters = fq_device, None
         self.bam_device, self.bam_counters = bam_device, None
+        # groupsort: (path, a call that gives the device) -- the tool-stage records' BAM, a second
+        # BamWriter fed from Consensus.toolrec; put()'s gcuts are its cuts, as family indices
+        self.groupsort, self.groupsort_counters = groupsort, {"records": 0, "raw_bytes": 0}
         self.T = {"records": 0.0, "encode": 0.0, "writer_wait": 0.0}
         self.records_out = 0
         self.outs, self.recq = queue.Queue(maxsize=1), queue.Queue(maxsize=1)  # consensus -> builder -> writer
         self.workers = [threading.Thread(target=f, name="stream" + f.__name__, daemon=True)
                         for f in (self._builder, self._writer)]
 
-    def put(self, cons, chunk: Chunk, cuts: Sequence = ()):
-        self.outs.put((cons, chunk, list(cuts)))
+    def put(self, cons, chunk: Chunk, cuts: Sequence = (), gcuts: Sequence = ()):
+        self.outs.put((cons, chunk, list(cuts), list(gcuts)))
 
     def _builder(self):  # the output records of a chunk, while the writer compresses the one before
         try:
@@ -370,8 +384,9 @@ class BackEnd(_Stages):
                 self.T["writer_wait"] += time.perf_counter() - t0
                 if item is None:
                     break
-                cons, chunk, cuts = item
+                cons, chunk, cuts, gcuts = item
                 t0 = time.perf_counter()
+                trec = (cons.toolrec, gcuts) if self.groupsort is not None else None
                 text = cons.fastq if self.fq_device is not None else None
                 brec = cons.bamrec if self.bam_device is not None else None
                 # (the FASTQ pair's device text reads no records, nor do the BAM's device records)
@@ -383,7 +398,7 @@ class BackEnd(_Stages):
                 self.T["records"] += time.perf_counter() - t0
                 chunk.raw = chunk.plan = chunk.batches = None
                 del item, cons
-                self.recq.put((recs, tags_buf, chunk, cuts, text, brec))
+                self.recq.put((recs, tags_buf, chunk, cuts, text, brec, trec))
         except BaseException as e:  # noqa: BLE001
             self.fault(e)
             while self.outs.get() is not None:  # drain so that put() never blocks
@@ -392,7 +407,7 @@ class BackEnd(_Stages):
             self.recq.put(None)
 
     def _writer(self):
-        w = fq = None
+        w = fq = g = None
         th = self.threads
         try:
             gz = (lambda: bgzf.GpuBgzf(self.gz_device())) if self.gz_device is not None else (lambda: None)
@@ -404,17 +419,23 @@ class BackEnd(_Stages):
                 fq = bgzf.FastqWriter(self.fastq[0], self.fastq[1], self.level,
                                       bgzf.GpuBgzf(self.fq_device()) if self.fq_device is not None else gz(),
                                       self.fragment is not None)
-            self.marks.append(((0, 0, 0), self.first_key))  # (a first piece holds the header, if any)
+            if self.groupsort is not None:
+                from . import toolrec as _toolrec
+                g = bgzf.BamWriter(self.groupsort[0], _toolrec.header(self.header), self.level,
+                                   bgzf.GpuBgzf(self.groupsort[1]()), self.fragment)
+            self.marks.append(((0, 0, 0, 0), self.first_key))  # (a first piece holds the header, if any)
             while True:
                 item = self.recq.get()
                 if item is None:
                     break
-                recs, tags_buf, chunk, cuts, text, brec = item
+                recs, tags_buf, chunk, cuts, text, brec, trec = item
                 t1 = time.perf_counter()
-                a = 0
+                a = ga = 0
                 n_out = recs.n if recs is not None else 2 * sum(x.kept for x in (text if text is not None else brec))
                 part = None
-                for idx, key in cuts + [(n_out, None)]:
+                n_fam = sum(x.fams for x in trec[0]) if trec is not None else 0
+                gcuts = (trec[1] if trec is not None else [0] * len(cuts)) + [n_fam]
+                for (idx, key), gidx in zip(cuts + [(n_out, None)], gcuts):
                     if recs is not None:
                         part = recs if (a == 0 and idx == n_out) else _slice_records(recs, a, idx)
                     if idx > a:
@@ -426,14 +447,20 @@ class BackEnd(_Stages):
                             fq.add_device(_text_ranges(text, a // 2, idx // 2), th)
                         elif fq is not None:
                             fq.add(part, th)
+                    if g is not None and gidx > ga:
+                        _add_toolrec(g, trec[0], ga, gidx, th)
                     if key is not None:  # everything so far leaves as whole blocks; a piece starts here
                         bo = w.flush(th) if w is not None else 0
                         fo = fq.flush(th) if fq is not None else (0, 0)
-                        self.marks.append(((bo, fo[0], fo[1]), (key[0], key[1], self.tie)))
-                    a = idx
+                        go = g.flush(th) if g is not None else 0
+                        self.marks.append(((bo, fo[0], fo[1], go), (key[0], key[1], self.tie)))
+                    a, ga = idx, gidx
                 self.records_out += n_out
                 self.T["encode"] += time.perf_counter() - t1
-                del item, recs, part, text, brec  # (the device bytes are released here, the job that reads them submitted)
+                if trec is not None:
+                    self.groupsort_counters["records"] += sum(x.n_rec for x in trec[0])
+                    self.groupsort_counters["raw_bytes"] += sum(int(x.foff[-1]) for x in trec[0])
+                del item, recs, part, text, brec, trec  # (the device bytes are released here, the job that reads them submitted)
                 # (the chunk's records are written; nothing refers to their arrays)
                 self.bufs.give(chunk.pool_buf)
                 self.bufs.give(tags_buf)
@@ -450,9 +477,11 @@ class BackEnd(_Stages):
                 fq.close(th)
                 if self.fq_device is not None:
                     self.fastq_counters = fq.gpu.counters()
+            if g is not None:
+                g.close(th)
         except BaseException as e:  # noqa: BLE001
             self.fault(e)
-            bgzf.close_quietly(w, fq)
+            bgzf.close_quietly(w, fq, g)
             while self.recq.get() is not None:  # drain so the builder never blocks
                 pass
 
@@ -470,17 +499,19 @@ def step5_stream(in_bam: str, fasta: str, out_bam: Optional[str], engine=None, p
                  batch_bases: Optional[int] = None, stats: Optional[dict] = None, gpu_bgzf: bool = False,
                  defer: Optional[int] = None, read_size: int = 8 << 20, filter=None, gpu_inflate: bool = False,
                  gpu_fastq: bool = False, gpu_bam: bool = False, gpu_image: bool = False,
-                 metrics: Optional[str] = None, metrics_cycles: int = 512) -> dict:
+                 metrics: Optional[str] = None, metrics_cycles: int = 512, groupsort_bam: Optional[str] = None) -> dict:
     """step5 in bounded memory, pipelined (run); defer: the span past which a template is
     deferred (default DEFAULT_DEFER_SPAN; 0 = off); read_size: compressed bytes per refill;
     filter: as step5's; gpu_inflate: the input's BGZF blocks inflate on the GPU (bgzf.GpuInflate);
     gpu_fastq: the FASTQ pair is formatted, checksummed and deflated on the GPU (StreamJob);
     gpu_bam: the BAM's records are written, checksummed and deflated on the GPU (StreamJob);
     gpu_image: the family images are made on the GPU from the records' bytes (StreamJob);
-    metrics: the run's consensus metrics, reduced on the GPU, written to this JSON file (StreamJob)."""
+    metrics: the run's consensus metrics, reduced on the GPU, written to this JSON file (StreamJob);
+    groupsort_bam: the records after tool 1 and tool 2, encoded on the GPU, written to this BAM (StreamJob)."""
     job = StreamJob(in_bam, fasta, out_bam, fastq, prefix, threads, level, tags, gpu_bgzf, chunk_bytes, slack,
                     batch_bases, read_size, filter=filter, defer=defer, gpu_inflate=gpu_inflate, gpu_fastq=gpu_fastq,
-                    gpu_bam=gpu_bam, gpu_image=gpu_image, metrics=metrics, metrics_cycles=metrics_cycles)
+                    gpu_bam=gpu_bam, gpu_image=gpu_image, metrics=metrics, metrics_cycles=metrics_cycles,
+                    groupsort_bam=groupsort_bam)
     return _public(run(job, engine, stats=stats))
 
 
@@ -510,14 +541,15 @@ def _public(info: dict) -> dict:
     return info
 
 
-def _family_cuts(cons, raw, plan, splices, strict: bool, start: int = 0):
+def _family_cuts(cons, raw, plan, splices, strict: bool, start: int = 0, fams: Optional[list] = None):
     """Output record indices where a chunk's BAM / FASTQ output is cut before each splice key, in
     order: (record index, key) per key used.  A family's key is its first record's coarse key
     (RawRecords.tc_key).  strict (the main stream): before the first family whose key exceeds the
     splice (no family lies within kDeferMargin of one); else (the spill's pass): before the first
     family whose key reaches the splice minus kDeferMargin (a deferred template's two records may
     estimate its key a few positions apart).  splices[start:] are tried; a key no family of the
-    chunk reaches is left (-> cuts, the index of the first key left)."""
+    chunk reaches is left (-> cuts, the index of the first key left).  fams: a list that receives
+    the family index of every cut (the tool-stage records' BAM is cut there: it holds every family)."""
     F = int(cons.status.shape[0])
     if F == 0 or splices.shape[0] <= start:
         return [], start
@@ -538,6 +570,8 @@ def _family_cuts(cons, raw, plan, splices, strict: bool, start: int = 0):
             f = int(np.argmax(hit))
         lo = max(lo, f)
         out.append((2 * int(em[lo]), (int(splices[j, 0]), int(splices[j, 1]))))
+        if fams is not None:
+            fams.append(int(lo))
         j += 1
     return out, j
 
@@ -568,6 +602,27 @@ def _text_ranges(text, a: int, b: int) -> list:
                 out[d] += r
         k0 += x.kept
     return out
+
+
+def _add_toolrec(g, pieces, a: int, b: int, threads: int):
+    """Families a..b-1 of a chunk whose batches' tool-stage records are `pieces` (pipeline.ToolrecPiece
+    each, in order) join the BAM writer g: device records as byte ranges (add_device), the host
+    twin's as raw records."""
+    dev, k0 = [], 0
+    for x in pieces:
+        lo, hi = max(a - k0, 0), min(b - k0, x.fams)
+        k0 += x.fams
+        if hi <= lo:
+            continue
+        if x.event is not None:
+            dev += x.ranges(lo, hi)
+            continue
+        if dev:
+            g.add_device([dev], threads)
+            dev = []
+        g.add_raw(x.host(lo, hi), threads)
+    if dev:
+        g.add_device([dev], threads)
 
 
 def _rec_ranges(brec, a: int, b: int) -> list:
@@ -606,7 +661,7 @@ def pieces_of(marks, paths, phase: int, rank: int) -> list:
 
 
 def assemble(dst: str, pieces, k: int):
-    """Output file k (0 the BAM, 1 / 2 the FASTQ pair) from the pieces in sort-key order, then one
+    """Output file k (0 the BAM, 1 / 2 the FASTQ pair, 3 the tool-stage records' BAM) from the pieces in sort-key order, then one
     BGZF EOF block; written aside and renamed over dst."""
     tmp = dst + ".asm"
     with open(tmp, "wb") as out:
@@ -652,6 +707,8 @@ def _run_chunk(eng, runner, ch: Chunk, mode: int, tags: bool, job: StreamJob, G:
         return pipeline.concat_consensus(parts)
     if ch.batches is None:  # (gpu_image: the whole-chunk path reads unpacked bases)
         mkw = {} if job.metrics is None else {"metrics": True}
+        if job.groupsort_bam is not None:
+            mkw["toolrec"] = "device"
         return pipeline.run_step5(eng, R.unpack_bases(ch.raw), tags=tags, batch_bases=job.batch_bases,
                                   filter=job.filter, **mkw)[0]
     fkw = {} if job.filter is None else {"filter": job.filter, "molecular": job.molecular is not None}
@@ -669,6 +726,9 @@ def _run_chunk(eng, runner, ch: Chunk, mode: int, tags: bool, job: StreamJob, G:
         tags = False
     if job.gpu_image:  # the batches carry no images: they are made in HBM from the chunk's bytes
         fkw.update(raw_bases=raw.raw_bases)
+    if job.groupsort_bam is not None:  # the records after the tools are written where their dump lies
+        from . import toolrec as _toolrec
+        fkw.update(toolrec=lambda fb: _toolrec.batch_tables(raw, fb))
     return pipeline.concat_consensus(pipeline.run_batches(eng, ch.batches, mode, tags, G, **fkw))
 
 
@@ -708,6 +768,13 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
         raise ValueError("metrics is not supported in a rank's stream yet (one process, one GPU)")
     if job.gpu_image and (job.rng is not None or job.owner is not None):
         raise ValueError("gpu_image is not supported in a rank's stream yet (one process, one GPU)")
+    if job.groupsort_bam is not None:
+        if runner is not None:
+            raise ValueError("a runner stream writes no groupsort_bam (one process, one GPU)")
+        if job.rng is not None or job.owner is not None:
+            raise ValueError("groupsort_bam is not supported in a rank's stream yet (one process, one GPU)")
+        if molecular:
+            raise ValueError("groupsort_bam applies to step 5 only: step 1 runs no tools")
     if job.gpu_fastq and job.fastq is None:
         raise ValueError("gpu_fastq needs the FASTQ pair (fastq=(path1, path2))")
     if job.gpu_bam and job.out_bam is None:
@@ -767,6 +834,7 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
                        tie=0 if late is not None else 1,  # (a spill piece sorts before the stream's piece of its key)
                        fq_device=(lambda: eng.device) if job.gpu_fastq else None,
                        bam_device=(lambda: eng.device) if job.gpu_bam else None,
+                       groupsort=(job.groupsort_bam, lambda: eng.device) if job.groupsort_bam is not None else None,
                        on_written=(lambda ch: pinned.give(ch.pin_buf)) if pinned is not None else None)
         pjob = dataclasses.replace(job, prefix=prefix)  # (the read names' prefix, resolved)
         mode = pipeline.MODE_VOTE if molecular else pipeline.MODE_CONVERT | pipeline.MODE_EXTEND | pipeline.MODE_VOTE
@@ -783,16 +851,16 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
                 info["chunks"] += 1
                 if job.filter is not None:
                     info["filter"] = _filter.add_summary(info["filter"], _filter.summary(cons))
-                cuts = []
+                cuts, gcuts = [], []
                 if late is not None:  # the spill's pass: cut before the families of each deferred key
-                    cuts, lj = _family_cuts(cons, ch.raw, ch.plan, late, False, lj)
+                    cuts, lj = _family_cuts(cons, ch.raw, ch.plan, late, False, lj, gcuts)
                 elif ch.splices is not None and ch.splices.shape[0]:
-                    cuts, _ = _family_cuts(cons, ch.raw, ch.plan, ch.splices, True)
+                    cuts, _ = _family_cuts(cons, ch.raw, ch.plan, ch.splices, True, fams=gcuts)
                     info["splices"].append(ch.splices)
                 if job.regions and cons.status.shape[0]:
                     rc, pair = _region_cuts(cons, ch.raw, ch.plan, pair)
                     cuts = sorted(cuts + rc)
-                back.put(cons, ch, cuts)
+                back.put(cons, ch, cuts, gcuts)
                 del ch, cons
         if inflater is not None:
             info["gpu_inflate"] = inflater.counters()
@@ -803,6 +871,8 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
                 info["gpu_fastq"] = back.fastq_counters
             if job.gpu_bam:
                 info["gpu_bam"] = back.bam_counters
+            if job.groupsort_bam is not None:
+                info["groupsort_bam"] = dict(back.groupsort_counters)
             info["records_out"] = back.records_out
             info["spilled_bytes"] = front.spilled_bytes
             info["deferred_families"] = int(rs.get("deferred", 0))
@@ -816,6 +886,8 @@ def run(job: StreamJob, engine=None, runner=None, stats: Optional[dict] = None, 
                 _metrics.write(job.metrics, eng.metrics_fetch(), job.metrics_cycles,
                                _metrics.run_params(eng.params, molecular, job.filter))
                 info["metrics"] = job.metrics
+            if job.groupsort_bam is not None and os.path.exists(job.groupsort_bam):
+                info["groupsort_bam"]["compressed_bytes"] = os.path.getsize(job.groupsort_bam)
     finally:
         flags.__exit__(None, None, None)
         if own:
@@ -838,7 +910,7 @@ def _finish_deferred(job: StreamJob, eng, runner, marks, spill_path: str, info: 
     out; else the spill's records as their own BAM through the stream (no deferral; cut at every
     deferred key), then the pieces of both outputs assembled in key order."""
     out_bam, fastq = job.out_bam, job.fastq
-    paths = [out_bam, fastq[0] if fastq else None, fastq[1] if fastq else None]
+    paths = [out_bam, fastq[0] if fastq else None, fastq[1] if fastq else None, job.groupsort_bam]
     if info["splices"].shape[0] == 0 and info["spilled_bytes"] == 0:
         for x in paths:
             if x is not None:
@@ -847,12 +919,14 @@ def _finish_deferred(job: StreamJob, eng, runner, marks, spill_path: str, info: 
         return
     base, sb = spill_path + ".p2", spill_path + ".p2.bam"
     p2 = [base + ".out.bam" if out_bam is not None else None,
-          base + ".1.fq.gz" if fastq else None, base + ".2.fq.gz" if fastq else None]
+          base + ".1.fq.gz" if fastq else None, base + ".2.fq.gz" if fastq else None,
+          base + ".gs.bam" if job.groupsort_bam is not None else None]
     try:
         info["deferred_records"] = write_spill_bam(sb, bam.read_bam_header(job.in_bam), [spill_path], 1, job.threads)
         mk2: list = []
         inf2 = run(dataclasses.replace(job, in_bam=sb, out_bam=p2[0], fastq=(p2[1], p2[2]) if fastq else None,
-                                       fragment="next", defer=0, late_splices=info["splices"], read_size=8 << 20),
+                                       fragment="next", defer=0, late_splices=info["splices"], read_size=8 << 20,
+                                       groupsort_bam=p2[3]),
                    eng, runner, marks=mk2)
         for k in ("records_in", "families", "families_emitted", "records_out"):
             info[k] += inf2[k]
@@ -860,12 +934,15 @@ def _finish_deferred(job: StreamJob, eng, runner, marks, spill_path: str, info: 
             info["gpu_fastq"] = {k: v + inf2["gpu_fastq"][k] for k, v in info["gpu_fastq"].items()}
         if "gpu_bam" in inf2:
             info["gpu_bam"] = {k: v + inf2["gpu_bam"][k] for k, v in info["gpu_bam"].items()}
+        if "groupsort_bam" in inf2:
+            for k in ("records", "raw_bytes"):
+                info["groupsort_bam"][k] += inf2["groupsort_bam"][k]
         if "gpu_inflate" in inf2:  # (the spill's BAM, inflated the same way)
             info["gpu_inflate_deferred"] = inf2["gpu_inflate"]
         if job.filter is not None:
             info["filter"] = _filter.add_summary(info["filter"], inf2["filter"])
         pieces = pieces_of(marks, paths, 0, 0) + pieces_of(mk2, p2, 1, 0)
-        for k in range(3):
+        for k in range(4):
             if paths[k] is not None:
                 assemble(paths[k], pieces, k)
     finally:

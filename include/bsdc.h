@@ -480,6 +480,61 @@ int32_t bsdc_metrics_filter_host(bsdc_ctx *ctx, const uint8_t *status, const uin
                                  int64_t n_fam, uint64_t *acc);
 const char *bsdc_metrics_last_error(void);
 
+/* (new exports, ABI 19 still) The records after tool 1 and tool 2 written on the device as BAM
+ * records (replaces the BAM writers of tools/1.convert_AG_to_CT.py and tools/2.extend_gap.py and
+ * fgbio SortBam -s TemplateCoordinate behind the rules convert_Bstrain, extend and
+ * groupsort_convert, main.snake.py:121-153: the file fgbio CallDuplexConsensusReads reads at :163;
+ * csrc/bsdc_toolrec.hip, DESIGN.md sections 3.10 and 8.11).  `out` is the bsdc_consensus of a
+ * bsdc_run(.. | BSDC_MODE_DUMP) (dump_pos, dump_len, dump_tags, dump_seq, dump_qual; the last two
+ * n_dump bytes each, 4-byte aligned) and rec the batch's record table (bsdc_family_batch.rec:
+ * rec[4 r] = record r's offset in dump_seq / dump_qual).  tab: one bsdc_toolrec_rec per batch
+ * record, the fields the tools leave as they are; names, cigar, aux: what its offsets point
+ * into -- the read names (no NUL), the cigar ops with the leading and trailing S op removed, the
+ * aux bytes (of a record tool 1 converts: with any RD / LA tag cut out).  Output record r is batch
+ * record r: off [n_rec + 1] receives the exclusive prefix sum of the records' byte counts (off[n_rec]
+ * = the total) and dst + off[r] the record: block_size; refID, pos = dump_pos, l_read_name, mapq,
+ * bin = reg2bin(pos, pos + max(the new cigar's reference length, 1)), n_cigar_op, flag, l_seq =
+ * dump_len, next_refID, next_pos, tlen; name NUL; the new cigar (tags bit1: 1M in front and, with
+ * bit0, the last op one shorter or gone at length 1; else bit2: 1M in front; bit3: 1M behind; ops
+ * never merged); the dump's nt16 codes two per byte, the pad nibble of an odd length 0; the dump's
+ * quals; the aux bytes; with bit1, RD:C:bit0 and LA:C:1.  No byte at or past dst + cap is written.
+ * bsdc_toolrec_bytes_bound = a size known before the launch, < 0 on a negative argument; tmp:
+ * bsdc_toolrec_tmp_bytes of 8-byte aligned scratch.  bsdc_toolrec_format: device pointers but for
+ * `out` itself and tab_host, the caller's host copy of tab, which is what gets checked; sizes,
+ * scan and records are enqueued on `stream` (hipStream_t) by the one call, after the bsdc_run on
+ * it.  bsdc_toolrec_host: host pointers, the same per-record functions run sequentially on the CPU
+ * (no GPU needed) -- the twin the tests compare the kernel with, and the whole-file path's encoder.
+ * BSDC_EINVAL, before anything is enqueued, with the reason in bsdc_toolrec_last_error (thread-
+ * local): a NULL pointer (the dump buffers included), a negative count, a cap below the bound, a
+ * misaligned buffer, a table entry that leaves names / cigar / aux, a name outside 1..254 bytes,
+ * more than 65533 ops, more than 2^24 aux bytes; bsdc_toolrec_host also: a record whose dump slot
+ * (rec[4 r] + dump_len[r]) leaves n_dump.  The launcher cannot read rec[] and dump_len, which lie
+ * in HBM: there the kernel gives such a record l_seq 0 and reads nothing outside the dump, so the
+ * caller passes the n_dump its dump buffers really hold. */
+typedef struct {
+    int64_t name_off;    /* first byte of the read name in names */
+    int64_t cig_off;     /* first op in cigar */
+    int64_t aux_off;     /* first aux byte in aux */
+    int32_t aux_len;
+    int32_t n_cig;       /* ops, clips removed */
+    int32_t ref_id, next_ref_id, next_pos, tlen;
+    uint16_t flag;
+    uint8_t mapq;
+    uint8_t name_len;    /* without the NUL */
+    int32_t reserved;
+} bsdc_toolrec_rec;
+
+int64_t bsdc_toolrec_bytes_bound(int64_t n_rec, int64_t name_bytes, int64_t n_ops, int64_t aux_bytes, int64_t n_dump);
+int64_t bsdc_toolrec_tmp_bytes(int64_t n_rec);
+int32_t bsdc_toolrec_format(const bsdc_consensus *out, const uint32_t *rec, int64_t n_rec, int64_t n_dump,
+                            const bsdc_toolrec_rec *tab, const bsdc_toolrec_rec *tab_host, const uint8_t *names,
+                            int64_t name_bytes, const uint32_t *cigar, int64_t n_ops, const uint8_t *aux, int64_t aux_bytes,
+                            int64_t *off, uint8_t *dst, int64_t cap, uint8_t *tmp, void *stream);
+int32_t bsdc_toolrec_host(const bsdc_consensus *out, const uint32_t *rec, int64_t n_rec, int64_t n_dump,
+                          const bsdc_toolrec_rec *tab, const uint8_t *names, int64_t name_bytes, const uint32_t *cigar,
+                          int64_t n_ops, const uint8_t *aux, int64_t aux_bytes, int64_t *off, uint8_t *dst, int64_t cap);
+const char *bsdc_toolrec_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif
