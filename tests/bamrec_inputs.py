@@ -52,8 +52,10 @@ class BamRecInput:
 SPECIAL_LEN = lambda stride: [0, 1, 2, 3, 4, 5, min(7, stride - 3) | 1, stride - 2]  # noqa: E731
 
 
-def make(stride: int, n_fam: int = 300, seed: int = 0, written: str = "mixed") -> BamRecInput:
-    """written: "mixed" (unemitted and filtered families at the front, at the back and in runs),
+def make(stride: int, n_fam: int = 300, seed: int = 0, written: str = "mixed", vector_tables: bool = False) -> BamRecInput:
+    """vector_tables: the name and the aux table out of one draw each (other bytes than the per-family
+    draws give): for a batch too large for them.
+    written: "mixed" (unemitted and filtered families at the front, at the back and in runs),
     "none", "all", "first_off" / "last_off" (only that family unemitted).  n_fam >= 40 places every
     edge of the module docstring (notes says where); every name length 1..253 occurs from 300 on."""
     rng = np.random.default_rng(seed)
@@ -96,10 +98,9 @@ def make(stride: int, n_fam: int = 300, seed: int = 0, written: str = "mixed") -
     ss_err[::7] = rng.integers(0, 256, ss_err[::7].shape).astype(np.uint8)
     # strands: 0 both, 1 AB only, 2 BA only, 3 R1 from AB alone and R2 from both
     strands = rng.integers(0, 4, F)
-    for f in range(F):
-        n = np.maximum(length[f], 1)
-        ss_len[f] = {0: [n[0], n[1], n[0], n[1]], 1: [n[0], n[1], 0, 0], 2: [0, 0, n[0], n[1]],
-                     3: [n[0], n[1], 0, n[1]]}[int(strands[f])]
+    n = np.maximum(length, 1)
+    ss_len[:, 0], ss_len[:, 1] = np.where(strands != 2, n[:, 0], 0), np.where(strands != 2, n[:, 1], 0)
+    ss_len[:, 2], ss_len[:, 3] = np.where(strands % 2 == 0, n[:, 0], 0), np.where(strands != 1, n[:, 1], 0)
     notes = {}
     kept = np.nonzero(((status & 1) != 0) & (filt == 0))[0]
     free = [int(f) for f in kept if f % 3 == 2]  # (their lengths are not the special ones)
@@ -181,19 +182,32 @@ def make(stride: int, n_fam: int = 300, seed: int = 0, written: str = "mixed") -
                 ss_qual[f, d, :take] = q[k:k + take]
                 ss_qual[f, 3 - d, :take] = q[k:k + take][::-1]
                 k += take
+            if k >= 256:
+                break
     nl = rng.integers(1, 12, F)
     nl[:6] = [1, 2, 3, 4, 5, 253][:min(F, 6)]
     nl[-1] = 253
     if F >= 270:
         nl[8:8 + 253] = np.arange(1, 254)
     alphabet = np.frombuffer(b"ACGTNacgt0123456789:/-_", np.uint8)
-    names = bam.StringTable.from_list([bytes(alphabet[rng.integers(0, alphabet.shape[0], int(n))]) for n in nl])
     auxs = []
-    for f in range(F):
-        mi = b"RGZA\0MIZ%d\0" % (f * 7)
-        rx = b"RXZ" + bytes(np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, 8)]) + b"-" + \
-            bytes(np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, int(rng.integers(1, 9)))]) + b"\0"
-        auxs.append([b"", mi, mi + rx, mi + rx][f % 4])
+    if vector_tables:
+        off = np.zeros(F + 1, np.int64)
+        np.cumsum(nl, out=off[1:])
+        names = bam.StringTable(alphabet[rng.integers(0, alphabet.shape[0], int(off[-1]))], off)
+        m = rng.integers(1, 9, F)
+        acgt = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, 16 * F)].tobytes()
+        for f in range(F):
+            mi = b"RGZA\0MIZ%d\0" % (f * 7)
+            auxs.append(mi + b"RXZ" + acgt[16 * f:16 * f + 8] + b"-" + acgt[16 * f + 8:16 * f + 8 + m[f]] + b"\0"
+                        if f % 4 >= 2 else mi if f % 4 else b"")
+    else:
+        names = bam.StringTable.from_list([bytes(alphabet[rng.integers(0, alphabet.shape[0], int(n))]) for n in nl])
+        for f in range(F):
+            mi = b"RGZA\0MIZ%d\0" % (f * 7)
+            rx = b"RXZ" + bytes(np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, 8)]) + b"-" + \
+                bytes(np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, int(rng.integers(1, 9)))]) + b"\0"
+            auxs.append([b"", mi, mi + rx, mi + rx][f % 4])
     aux = bam.StringTable.from_list(auxs)
     W = len(wd)
     return BamRecInput(stride, status, length, seq, qual, filt, names, aux, ss_len, ss_base, ss_qual, ss_depth, ss_err,
@@ -210,12 +224,9 @@ def records(x: BamRecInput, fams: np.ndarray, molecular: bool, tags: bool) -> "b
     seq_off = np.zeros(n + 1, np.int64)
     seq_off[1:] = np.cumsum(L)
     codes = np.stack([x.seq >> 4, x.seq & 15], axis=-1).reshape(x.n_fam, 2, x.stride)
-    seq = np.zeros(int(seq_off[-1]), np.uint8)
-    qual = np.zeros(int(seq_off[-1]), np.uint8)
-    for k in range(n):
-        f, d = int(fams[k // 2]), k & 1
-        seq[seq_off[k]:seq_off[k + 1]] = codes[f, d, :L[k]]
-        qual[seq_off[k]:seq_off[k + 1]] = x.qual[f, d, :L[k]]
+    row = 2 * np.repeat(fams, 2) + np.tile(np.arange(2), fams.shape[0])
+    idx = np.repeat(row * x.stride - seq_off[:-1], L) + np.arange(int(seq_off[-1]), dtype=np.int64)
+    seq, qual = codes.reshape(-1)[idx], x.qual.reshape(-1)[idx]
     two = np.repeat(fams, 2)
     names, aux = bam._take_table(x.names, two), bam._take_table(x.aux, two)
     tg = None

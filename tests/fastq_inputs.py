@@ -30,8 +30,17 @@ class FastqInput:
         return k & (self.filt == 0) if with_filt else k
 
 
-def make(stride: int, n_fam: int = 300, seed: int = 0, written: str = "mixed") -> FastqInput:
-    """written: "mixed" (unemitted and filtered families at the front, at the back and in runs),
+def random_names(rng, nl) -> "bam.StringTable":
+    """names of the lengths nl out of one draw: the table of a batch too large for a draw per name"""
+    alphabet = np.frombuffer(b"ACGTNacgt0123456789:/-_", np.uint8)
+    off = np.zeros(nl.shape[0] + 1, np.int64)
+    np.cumsum(nl, out=off[1:])
+    return bam.StringTable(alphabet[rng.integers(0, alphabet.shape[0], int(off[-1]))], off)
+
+
+def make(stride: int, n_fam: int = 300, seed: int = 0, written: str = "mixed", vector_names: bool = False) -> FastqInput:
+    """vector_names: the name table by random_names (other names than the per-name draws give).
+    written: "mixed" (unemitted and filtered families at the front, at the back and in runs),
     "none" (no family emitted), "all", "first_off" / "last_off" (only that family unemitted).
     Lengths 0, 1, 2, 3, 4, 5, an odd value and stride - 2 recur; name lengths 1..5, 254 and every
     length 1..254 once n_fam allows; every nt16 code and every quality byte 0..255 occur."""
@@ -80,14 +89,24 @@ def make(stride: int, n_fam: int = 300, seed: int = 0, written: str = "mixed") -
                 take = min(n, 256 - k) if k < 256 else 0
                 qual[f, d, :take] = q[k:k + take]
                 k += take
+            if k >= 256:
+                break
     nl = rng.integers(1, 12, F)
     nl[:6] = [1, 2, 3, 4, 5, 254][:min(F, 6)]
     nl[-1] = 254
     if F >= 270:
         nl[8:8 + 254] = np.arange(1, 255)
+    if vector_names:
+        return FastqInput(stride, status, length, seq, qual, filt, random_names(rng, nl))
     alphabet = np.frombuffer(b"ACGTNacgt0123456789:/-_", np.uint8)
     names = bam.StringTable.from_list([bytes(alphabet[rng.integers(0, alphabet.shape[0], int(n))]) for n in nl])
     return FastqInput(stride, status, length, seq, qual, filt, names)
+
+
+def gather_index(fams, L, seq_off, stride) -> np.ndarray:
+    """where the bases of records 2k, 2k + 1 = rows (fams[k], 0), (fams[k], 1) lie in a flattened [F, 2, stride] array"""
+    row = 2 * np.repeat(np.asarray(fams, np.int64), 2) + np.tile(np.arange(2), fams.shape[0])
+    return np.repeat(row * stride - seq_off[:-1], L) + np.arange(int(seq_off[-1]), dtype=np.int64)
 
 
 def records(x: FastqInput, fams: np.ndarray) -> "bam.OutRecordsBam":
@@ -98,13 +117,9 @@ def records(x: FastqInput, fams: np.ndarray) -> "bam.OutRecordsBam":
     seq_off = np.zeros(n + 1, np.int64)
     seq_off[1:] = np.cumsum(L)
     codes = np.stack([x.seq >> 4, x.seq & 15], axis=-1).reshape(x.n_fam, 2, x.stride)
-    seq = np.zeros(int(seq_off[-1]), np.uint8)
-    qual = np.zeros(int(seq_off[-1]), np.uint8)
-    for k in range(n):
-        f, d = int(fams[k // 2]), k & 1
-        seq[seq_off[k]:seq_off[k + 1]] = codes[f, d, :L[k]]
-        qual[seq_off[k]:seq_off[k + 1]] = x.qual[f, d, :L[k]]
-    names = bam.StringTable.from_list([x.names[int(f)] for f in np.repeat(fams, 2)])
+    idx = gather_index(fams, L, seq_off, x.stride)
+    seq, qual = codes.reshape(-1)[idx], x.qual.reshape(-1)[idx]
+    names = bam._take_table(x.names, np.repeat(fams, 2))
     empty = bam.StringTable(np.zeros(0, np.uint8), np.zeros(n + 1, np.int64))
     return bam.OutRecordsBam(
         flag=np.tile(np.asarray([77, 141], np.uint16), n // 2), tid=np.full(n, -1, np.int32),

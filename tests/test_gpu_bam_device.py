@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 EOF_BLOCK = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 DEV = "cuda:0"
 GUARD = 64
+CARRY_FAMS = 262145 + 1025  # 258 workgroups of the offset scan (bsdc_devtext.h): a tile of 256 and two more
 
 
 # ---- 1. the format kernel alone
@@ -86,11 +87,13 @@ def test_format_equals_the_host_encoder(tmp_path, stride, with_filt, molecular, 
 
 
 @pytest.mark.parametrize("written,n_fam", [("none", 300), ("all", 1), ("first_off", 300), ("last_off", 300),
-                                           ("all", 1025), ("mixed", 2500)])
+                                           ("all", 1025), ("mixed", 2500), ("mixed", CARRY_FAMS)])
 def test_format_family_patterns(tmp_path, written, n_fam):
-    """no family written (total 0), one family, the first / last family unwritten, and more
-    families than one scan workgroup takes (1024)"""
-    x = BI.make(32, n_fam, seed=n_fam, written=written)
+    """no family written (total 0), one family, the first / last family unwritten, more families
+    than one scan workgroup takes (1024), and more workgroups than k_scan_scan takes in one tile
+    (256: the second tile starts from the first one's carry)"""
+    big = n_fam == CARRY_FAMS
+    x = BI.make(16 if big else 32, n_fam, seed=n_fam, written=written, vector_tables=big)
     _, want = _check(x, False, False, True, tmp_path)
     if written == "none":
         assert want == b""

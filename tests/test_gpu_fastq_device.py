@@ -59,6 +59,7 @@ def test_crc32_refusals():
 # ---- 2. the format kernel alone
 
 GUARD = 64
+CARRY_FAMS = 262145 + 1025  # 258 workgroups of the offset scan (bsdc_devtext.h): a tile of 256 and two more
 
 
 class _Call:
@@ -124,11 +125,13 @@ def test_format_equals_the_host_writer(tmp_path, stride, with_filt):
 
 
 @pytest.mark.parametrize("written,n_fam", [("none", 300), ("all", 1), ("first_off", 300), ("last_off", 300),
-                                           ("all", 1025), ("mixed", 2500)])
+                                           ("all", 1025), ("mixed", 2500), ("mixed", CARRY_FAMS)])
 def test_format_family_patterns(tmp_path, written, n_fam):
-    """no family written (totals 0), one family, the first / last family unwritten, and more
-    families than one scan workgroup takes (1024)"""
-    x = FI.make(32, n_fam, seed=n_fam, written=written)
+    """no family written (totals 0), one family, the first / last family unwritten, more families
+    than one scan workgroup takes (1024), and more workgroups than k_scan_scan takes in one tile
+    (256: the second tile starts from the first one's carry)"""
+    big = n_fam == CARRY_FAMS
+    x = FI.make(16 if big else 32, n_fam, seed=n_fam, written=written, vector_names=big)
     _, want = _check(x, False, tmp_path)
     if written == "none":
         assert want == (b"", b"")

@@ -26,39 +26,48 @@ def _dev(a, dev):
     return torch.from_numpy(a.view(np.uint8) if a.size else np.zeros(8, np.uint8)).to(dev)
 
 
-def device_format(engine, c: TI.Case, extra=64, cap=None, null=None):
-    """bsdc_toolrec_format on a fabricated case -> (rc, off, buf); the buffer prefilled with GUARD"""
+def device_format(engine, c: TI.Case, extra=64, cap=None, null=None, *, dst_shift=0, n_dump=None, alloc=None, fetch=True):
+    """bsdc_toolrec_format on a fabricated case -> (rc, off, buf); the buffer prefilled with GUARD.
+    dst_shift: the destination starts that many bytes into the buffer (which is 8 bytes longer);
+    n_dump: what the call is told in place of the dump's size (the device buffers keep theirs);
+    alloc: the buffer's size where cap is not to decide it; fetch=False: off and buf stay on the device."""
     lib, dev = engine.lib, engine.device
-    t = toolrec.tables(c.raw, np.arange(c.raw.n), c.conv)
+    t = c.tables()
     n = t.n
-    n_dump = c.dump_seq.shape[0] // 4 * 4
+    n_have = c.dump_seq.shape[0] // 4 * 4
+    n_dump = n_have if n_dump is None else n_dump
+    assert 0 <= n_dump <= n_have and 0 <= dst_shift < 8
     cap = t.bound(n_dump) + extra if cap is None else cap
     rec = np.zeros((max(n, 1), 4), np.uint32)
     rec[:n, 0] = c.rec_off
-    d = {k: _dev(v, dev) for k, v in dict(pos=c.dump_pos, len=c.dump_len, tags=c.dump_tags, seq=c.dump_seq[:n_dump],
-                                          qual=c.dump_qual[:n_dump], rec=rec, tab=t.tab, names=t.names, cigar=t.cigar,
+    d = {k: _dev(v, dev) for k, v in dict(pos=c.dump_pos, len=c.dump_len, tags=c.dump_tags, seq=c.dump_seq[:n_have],
+                                          qual=c.dump_qual[:n_have], rec=rec, tab=t.tab, names=t.names, cigar=t.cigar,
                                           aux=t.aux).items()}
     o = _lib.ConsensusC()
     o.dump_pos, o.dump_len, o.dump_tags = d["pos"].data_ptr(), d["len"].data_ptr(), d["tags"].data_ptr()
     o.dump_seq, o.dump_qual = d["seq"].data_ptr(), d["qual"].data_ptr()
     if null:
         setattr(o, null, None)
-    buf = torch.full((max(cap, 16),), GUARD, dtype=torch.uint8, device=dev)
+    size = (max(cap, 16) + (8 if dst_shift else 0)) if alloc is None else alloc
+    assert size >= dst_shift + cap  # (whatever the kernel does up to cap stays inside the allocation)
+    buf = torch.full((size,), GUARD, dtype=torch.uint8, device=dev)
     off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     tmp = torch.empty(int(lib.bsdc_toolrec_tmp_bytes(n)), dtype=torch.uint8, device=dev)
     tab_h = np.ascontiguousarray(t.tab) if n else np.zeros(1, _lib.TOOLREC_REC)
     s = torch.cuda.current_stream(dev)
     rc = lib.bsdc_toolrec_format(C.byref(o), d["rec"].data_ptr(), n, n_dump, d["tab"].data_ptr(), tab_h.ctypes.data,
                                  d["names"].data_ptr(), t.names.shape[0], d["cigar"].data_ptr(), t.cigar.shape[0],
-                                 d["aux"].data_ptr(), t.aux.shape[0], off.data_ptr(), buf.data_ptr(), cap, tmp.data_ptr(),
-                                 C.c_void_p(s.cuda_stream))
+                                 d["aux"].data_ptr(), t.aux.shape[0], off.data_ptr(), buf.data_ptr() + dst_shift, cap,
+                                 tmp.data_ptr(), C.c_void_p(s.cuda_stream))
     s.synchronize()
+    if not fetch:
+        return rc, off, buf
     return rc, off.cpu().numpy(), buf.cpu().numpy()
 
 
 @pytest.mark.parametrize("name", TI.NAMES)
 def test_kernel_equals_the_twin(engine, name):
-    c = TI.build(TI.make(name))
+    c = TI.build_named(name)
     want_off, want = twin(c)
     rc, off, buf = device_format(engine, c)
     assert rc == 0, engine.lib.bsdc_toolrec_last_error().decode()

@@ -23,11 +23,28 @@ GUARD = 0x5C
 
 
 def twin(c: TI.Case, extra=64):
-    t = toolrec.tables(c.raw, np.arange(c.raw.n), c.conv)
+    t = c.tables()
     n_dump = c.dump_seq.shape[0] // 4 * 4
     cap = t.bound(n_dump) + extra
     off, buf = toolrec.host(t, c.rec_off, c.dump_pos, c.dump_len, c.dump_tags, c.dump_seq, c.dump_qual, cap=cap, fill=GUARD)
     return off, buf
+
+
+def twin_call(c: TI.Case, n_dump=None, cap=None, alloc=None):
+    """bsdc_toolrec_host with n_dump and cap as given (default: the dump's own size, the bound) on a
+    buffer of `alloc` GUARD bytes -> (rc, off, buf)"""
+    t = c.tables()
+    n = t.n
+    rec = np.zeros((max(n, 1), 4), np.uint32)
+    rec[:n, 0] = c.rec_off
+    n_dump = c.dump_seq.shape[0] // 4 * 4 if n_dump is None else n_dump
+    cap = t.bound(n_dump) if cap is None else cap
+    buf, off = np.full(max(cap, 1) if alloc is None else alloc, GUARD, np.uint8), np.zeros(n + 1, np.int64)
+    o = toolrec._consensus_c(c.dump_pos, c.dump_len, c.dump_tags, c.dump_seq, c.dump_qual)
+    rc = _lib.load().bsdc_toolrec_host(C.byref(o), rec.ctypes.data, n, n_dump, t.tab.ctypes.data, t.names.ctypes.data,
+                                       t.names.shape[0], t.cigar.ctypes.data, t.cigar.shape[0], t.aux.ctypes.data,
+                                       t.aux.shape[0], off.ctypes.data, buf.ctypes.data, cap)
+    return rc, off, buf
 
 
 def test_exports_and_layout():
@@ -43,8 +60,8 @@ def test_exports_and_layout():
 
 @pytest.mark.parametrize("name", TI.NAMES)
 def test_twin_equals_the_restatement(name):
-    recs = TI.make(name)
-    c = TI.build(recs)
+    c = TI.build_named(name)
+    recs = c.recs
     off, buf = twin(c)
     want_off, want = TR.stream(recs)
     assert np.array_equal(off, want_off), name
@@ -70,6 +87,110 @@ def test_sets_hold_their_edges():
     assert TR.reg2bin((1 << 14) - 5, (1 << 14) + 6) == 585 and TR.reg2bin((1 << 17) - 100, (1 << 17) + 111) == 73
     assert TR.new_aux(b"XBBC\x06\0\0\0RDCLAC" + b"RDC\x01", 7) == b"XBBC\x06\0\0\0RDCLAC" + b"RDC\x01LAC\x01"
     assert TR.new_aux(b"RDC\x01MIZ1\0", 0) == b"RDC\x01MIZ1\0"
+    _later_sets_hold_their_edges()
+
+
+def _bin(r, ops):
+    n = TI.ref_len(ops)
+    return TR.reg2bin(r["pos"], r["pos"] + (n if n > 0 else 1))
+
+
+def _later_sets_hold_their_edges():
+    """test_sets_hold_their_edges, the sets that came later"""
+    # longcigar: the ops a lane reads in a second round decide the bin
+    recs = TI.make("longcigar")
+    second = 0
+    for r in recs:
+        ops = TR.new_cigar(r["cigar"], r["tags"])
+        assert ops == TI.new_ops(r)
+        if len(ops) > 64:
+            assert _bin(r, ops) != _bin(r, ops[:64]), r["name"]
+            second += 1
+    n_out = {len(TR.new_cigar(r["cigar"], r["tags"])) for r in recs}
+    assert second >= 40 and {63, 64, 65, 66, 128, 129, 130, 131, 1000, 1002, 65533, 65535} <= n_out
+    assert max(n_out) == 65535 and max(len(TR.strip_clips(r["cigar"])) for r in recs) == TI.MAX_OPS == 65533
+    for n in TI.LONG_OPS:  # RD drops a last op of length 1 and shortens a longer one, at every count
+        ends = {(r["tags"], r["cigar"][-1 - (r["cigar"][-1] & 15 == TI.S)] >> 4) for r in recs
+                if len(TR.strip_clips(r["cigar"])) == n}
+        assert {(7, 1), (7, 5), (15, 1), (15, 5), (0, 1), (6, 5)} <= ends, n
+    lanes = set()
+    for r in recs:
+        lanes |= {j % 64 for j, o in enumerate(TR.new_cigar(r["cigar"], r["tags"])) if (o & 15) in TR.REF_OPS and j >= 64}
+    assert lanes == set(range(64))
+    # hugeref: the sum's high half decides the bin
+    recs = TI.make("hugeref")
+    low_alone = 0
+    for r in recs:
+        ops = TR.new_cigar(r["cigar"], r["tags"])
+        n = TI.ref_len(ops)
+        assert n >= 1 << 32 and r["pos"] in (0, 1000) and _bin(r, ops) == 0
+        low = n & 0xFFFFFFFF
+        low_alone += TR.reg2bin(r["pos"], r["pos"] + (low if low > 0 else 1)) != 0
+        if low < 1 << 20:  # one lane's ops pass 2^32 alone, and it is not the lane that writes the bin
+            per = [sum(o >> 4 for j, o in enumerate(ops) if j % 64 == k and (o & 15) in TR.REF_OPS) for k in range(64)]
+            assert max(per) >= 1 << 32 and per[1] < 1 << 32
+    assert low_alone >= 5
+    # phases: every combination at every residue of the record's start
+    recs = TI.make("phases")
+    off = TR.stream(recs)[0]
+    assert np.array_equal(np.diff(off), [TI.size_of(r) for r in recs])
+    seen = {(int(off[k]) & 3, len(r["name"]), len(r["seq"]), len(r["aux"]), r["tags"]) for k, r in enumerate(recs) if k & 1}
+    P = TI.PHASES
+    assert seen == {(h, a, b, c, d) for h in range(4) for a in P["nl"] for b in P["L"] for c in P["al"] for d in P["tags"]}
+    assert {b & 7 for b in P["L"]} == {7, 0, 1} and len({bytes(r["qual"]) for r in recs}) > len(recs) - 8
+    # tight: the last record's bases end the dump, or a multiple of 4 does, with nothing behind
+    for L in TI.TIGHT:
+        c = TI.build_named("tight_%d" % L)
+        assert int(c.dump_len[-1]) == L and c.dump_seq.shape[0] == c.dump_qual.shape[0] == int(c.rec_off[-1]) + (L + 3) // 4 * 4
+    # the shared entries: the records outgrow the bound
+    c = TI.shared_case()
+    total = sum(len(TR.record_bytes(TI.record_of(c, r))) for r in range(c.n))
+    cap = c.tables().bound(c.dump_seq.shape[0])
+    assert c.n == 200 and total > cap + 4000 and total == int(TI.layout_sizes(c).sum())
+    e = c.tables().tab
+    assert (e["name_off"] == 0).all() and (e["cig_off"] == 0).all() and (e["aux_off"] == 0).all()
+    assert (e["name_len"] == 8).all() and (e["n_cig"] == 3).all() and (e["aux_len"] == 40).all()
+    assert len(set(c.rec_off.tolist())) == c.n
+    # the carry: one tile of workgroup sums, one more, and two more
+    assert [TI.scan_groups(n) for n in TI.CARRY_COUNTS] == [256, 257, 258]
+    assert TI.CARRY_COUNTS == (262144, 262145, 262144 + 1025)
+    assert [TI.scan_groups(int(n.split("_")[1])) for n in ("counts_1023", "counts_1024", "counts_1025")] == [1, 1, 2]
+
+
+def test_twin_stops_at_cap_with_shared_entries():
+    """cap = the bound exactly, the records' total beyond it: the offsets are whole, the bytes
+    below cap are the restatement's, and no byte at or past cap is written"""
+    c = TI.shared_case()
+    want_off, want = TR.stream([TI.record_of(c, r) for r in range(c.n)])
+    cap = c.tables().bound(c.dump_seq.shape[0])
+    total = int(want_off[-1])
+    k = int(np.searchsorted(want_off, cap, "right")) - 1
+    assert cap < total and cap % 4 == 2 and want_off[k] + 4 <= cap <= want_off[k + 1] - 4
+    rc, off, buf = twin_call(c, cap=cap, alloc=total + 64)
+    assert rc == 0, _lib.load().bsdc_toolrec_last_error().decode()
+    assert np.array_equal(off, want_off)
+    assert buf[:cap].tobytes() == want[:cap]
+    assert (buf[cap:] == GUARD).all()
+
+
+@pytest.fixture(scope="module")
+def carry_twin():
+    """the largest carry case through the twin once"""
+    c = TI.carry_case(TI.CARRY_COUNTS[-1])
+    return c, twin(c)
+
+
+def test_carry_case_twin_equals_the_restatement(carry_twin):
+    """the twin is what the kernel is compared with on the carry cases: its offsets against the
+    layout rule in numpy, its bytes against the restatement on 2,000 records picked at random"""
+    c, (off, buf) = carry_twin
+    sizes = TI.layout_sizes(c)
+    assert np.array_equal(off[1:], np.cumsum(sizes)) and off[0] == 0
+    assert (buf[int(off[-1]):] == GUARD).all()
+    assert set(c.dump_tags.tolist()) == {0, 6, 7, 15, 8, 4, 12} and set(c.tables().tab["n_cig"].tolist()) == {0, 1, 2}
+    for r in np.random.default_rng(1).choice(c.n, 2000, replace=False):
+        want = TR.record_bytes(TI.record_of(c, int(r)))
+        assert buf[int(off[r]):int(off[r + 1])].tobytes() == want, int(r)
 
 
 def _write(path, recs_bytes, hdr):
