@@ -45,6 +45,20 @@ TOOLREC_REC = [("name_off", "<i8"), ("cig_off", "<i8"), ("aux_off", "<i8"), ("au
                ("mapq", "u1"), ("name_len", "u1"), ("reserved", "<i4")]
 
 
+# bsdc_zip_rec / bsdc_zip_src as numpy records: cli zipper's tables (zipper.py)
+ZIP_REC = [("rec_off", "<i8"), ("part_off", "<i8"), ("rec_len", "<i4"), ("aux_start", "<i4"), ("part_len", "<i4"),
+           ("flag_or", "<u4")]
+ZIP_SRC = [("off", "<i8"), ("len", "<i4"), ("aux", "<i4"), ("ref_id", "<i4"), ("pos", "<i4"), ("flag", "<u2"),
+           ("name_len", "u1"), ("reserved0", "u1"), ("reserved", "<i4")]
+ZIP_MAX_TAGS = 32  # BSDC_ZIP_MAX_TAGS
+
+
+class ZipTagsC(C.Structure):  # bsdc_zip_tags
+    _fields_ = [("reverse", C.c_uint8 * (2 * ZIP_MAX_TAGS)), ("revcomp", C.c_uint8 * (2 * ZIP_MAX_TAGS)),
+                ("remove", C.c_uint8 * (2 * ZIP_MAX_TAGS)), ("n_reverse", C.c_int32), ("n_revcomp", C.c_int32),
+                ("n_remove", C.c_int32), ("reserved", C.c_int32)]
+
+
 # bsdc_image_rec as a numpy record: the gather's table (batch.FamilyBatch.gather)
 IMAGE_REC = [("src", "<i8"), ("l_seq", "<i4"), ("skip", "<i4"), ("len", "<i4"), ("slot", "<u4")]
 
@@ -81,7 +95,9 @@ EXPORTS = ("bsdc_abi_version", "bsdc_ctx_create", "bsdc_ctx_set_params", "bsdc_c
            "bsdc_image_gather", "bsdc_image_gather_host", "bsdc_image_last_error", "bsdc_metrics_words", "bsdc_metrics",
            "bsdc_metrics_filter", "bsdc_metrics_host", "bsdc_metrics_filter_host", "bsdc_metrics_last_error",
            "bsdc_toolrec_bytes_bound", "bsdc_toolrec_tmp_bytes", "bsdc_toolrec_format", "bsdc_toolrec_host",
-           "bsdc_toolrec_last_error")
+           "bsdc_toolrec_last_error", "bsdc_zip_sort_tile", "bsdc_zip_sort_tmp_bytes", "bsdc_zip_sort",
+           "bsdc_zip_sort_host", "bsdc_zip_bytes_bound", "bsdc_zip_format_tmp_bytes", "bsdc_zip_format",
+           "bsdc_zip_format_host", "bsdc_zip_scan_host", "bsdc_zip_last_error")
 
 _lib = None
 
@@ -194,6 +210,27 @@ def load(path: str = LIB_PATH):
                                       C.c_int64]
     lib.bsdc_toolrec_host.restype = C.c_int32
     lib.bsdc_toolrec_last_error.restype = C.c_char_p
+    lib.bsdc_zip_sort_tile.restype = C.c_int32
+    lib.bsdc_zip_sort_tmp_bytes.argtypes = [C.c_int64]
+    lib.bsdc_zip_sort_tmp_bytes.restype = C.c_int64
+    lib.bsdc_zip_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.bsdc_zip_sort.restype = C.c_int32
+    lib.bsdc_zip_sort_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32]
+    lib.bsdc_zip_sort_host.restype = C.c_int32
+    lib.bsdc_zip_bytes_bound.argtypes = [C.c_void_p, C.c_int64]
+    lib.bsdc_zip_bytes_bound.restype = C.c_int64
+    lib.bsdc_zip_format_tmp_bytes.argtypes = [C.c_int64]
+    lib.bsdc_zip_format_tmp_bytes.restype = C.c_int64
+    lib.bsdc_zip_format.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ZipTagsC), C.c_void_p, C.c_void_p,
+                                    C.c_int64, C.c_void_p, C.c_void_p]
+    lib.bsdc_zip_format.restype = C.c_int32
+    lib.bsdc_zip_format_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                         C.POINTER(ZipTagsC), C.c_void_p, C.c_void_p, C.c_int64]
+    lib.bsdc_zip_format_host.restype = C.c_int32
+    lib.bsdc_zip_scan_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+    lib.bsdc_zip_scan_host.restype = C.c_int64
+    lib.bsdc_zip_last_error.restype = C.c_char_p
     if lib.bsdc_abi_version() != BSDC_ABI_VERSION:
         raise RuntimeError("libbsdc ABI %d != %d" % (lib.bsdc_abi_version(), BSDC_ABI_VERSION))
     if path == LIB_PATH:

@@ -15,6 +15,12 @@ step5 --groupsort-bam PATH also writes the records after tool 1 and tool 2 in Te
 order: the file rule groupsort_convert leaves (main.snake.py:144-153), the input of fgbio
 CallDuplexConsensusReads at :163 (--gpus 1 only).
 
+    python -m bsseqconsensusreads_amd.cli zipper ALIGNED.bam UNMAPPED.bam OUT.bam [--tags-to-reverse T..]
+            [--tags-to-revcomp T..] [--tags-to-remove T..] [--info PATH]
+        rules mergeAunA_consensus and mergeAunA_consensus_grepaligned (main.snake.py:97-119): the aligner's
+        records with MI, RX, RG and the consensus tags put back from the step-1 BAM, unmapped records
+        dropped, coordinate-sorted on the GPU (both inputs are read whole)
+
 OUT.bam may be '-' to skip the BAM when only the FASTQ pair is wanted.  Errors exit non-zero with
 the message on stderr, so Snakemake aborts the rule and removes partial outputs, as it does for
 the reference tools (tools/2.extend_gap.py:179-180 raises on a record without MI).
@@ -119,7 +125,22 @@ def parse(argv):
         g.add_argument("--filter-min-mean-base-quality", type=int, default=None, metavar="Q", help="-q (default: off)")
         g.add_argument("--filter-require-single-strand-agreement", default=None, choices=("true", "false"),
                        help="-s: mask duplex bases whose two single-strand calls differ (default false)")
+    z = sub.add_parser("zipper")
+    z.add_argument("aligned", help="the aligner's BAM of the step-1 FASTQ pair (any order)")
+    z.add_argument("unmapped", help="the step-1 consensus BAM (unmapped records with MI, RX, RG and the consensus tags)")
+    z.add_argument("output", help="the coordinate-sorted, mapped-only BAM with the tags put back (step5's input)")
+    for opt, what in (("reverse", "reversed"), ("revcomp", "reverse-complemented")):
+        z.add_argument("--tags-to-" + opt, nargs="*", default=[], metavar="T",
+                       help="tags of the unmapped record that are %s on a reverse-strand record; Consensus = fgbio's "
+                            "per-base consensus tags (default: none, as main.snake.py:106)" % what)
+    z.add_argument("--tags-to-remove", nargs="*", default=[], metavar="T", help="tags left out of the output records")
+    z.add_argument("--threads", type=int, default=8)
+    z.add_argument("--level", type=int, default=6, help="the output's deflate level")
+    z.add_argument("--device", type=int, default=0)
+    z.add_argument("--info", default=None, metavar="PATH", help="write the run's counts as one JSON file")
     a = ap.parse_args(argv)
+    if a.cmd == "zipper":
+        return a
     others = [k for k in ("min_reads", "max_read_error_rate", "max_base_error_rate", "max_no_call_fraction",
                           "min_mean_base_quality", "require_single_strand_agreement")
               if getattr(a, "filter_" + k) is not None]
@@ -229,9 +250,24 @@ def _step5_fleet(a, gpus: int) -> int:
     return 0
 
 
+def _zipper(a) -> int:
+    """cli zipper: rules mergeAunA_consensus + mergeAunA_consensus_grepaligned on one GPU (zipper.zipper)."""
+    try:
+        from . import bam
+        info = bam.zipper(a.aligned, a.unmapped, a.output, a.tags_to_reverse, a.tags_to_revcomp, a.tags_to_remove,
+                          threads=a.threads, level=a.level, device=a.device, info=a.info)
+    except Exception as e:  # noqa: BLE001 -- the rule fails with the message
+        print("%s: %s" % (type(e).__name__, e), file=sys.stderr)
+        return 1
+    print(json.dumps(info), file=sys.stderr)
+    return 0
+
+
 def main(argv=None) -> int:
     argv = sys.argv[1:] if argv is None else list(argv)
     a = parse(argv)
+    if a.cmd == "zipper":
+        return _zipper(a)
     from . import bam, shard
     gpus = getattr(a, "gpus", 1)
     if gpus > 1 and "WORLD_SIZE" not in os.environ:

@@ -535,6 +535,82 @@ int32_t bsdc_toolrec_host(const bsdc_consensus *out, const uint32_t *rec, int64_
                           int64_t n_ops, const uint8_t *aux, int64_t aux_bytes, int64_t *off, uint8_t *dst, int64_t cap);
 const char *bsdc_toolrec_last_error(void);
 
+/* (new exports, ABI 19 still) cli zipper: the aligned consensus records with their unmapped
+ * partners' tags put back, in coordinate order (replaces `samtools sort -n | fgbio ZipperBams
+ * --sort Coordinate | samtools view -F 4`, rules mergeAunA_consensus and
+ * mergeAunA_consensus_grepaligned, main.snake.py:97-119; csrc/bsdc_zipper.hip, DESIGN.md sections
+ * 3.11 and 8.12).
+ *
+ * bsdc_zip_sort: keys [n] (refID << 32 | (pos + 1) << 1 | reverse) and their payload idx [n], device
+ * pointers, sorted in place by ascending key, equal keys in their order (a stable LSD radix sort,
+ * 8 bits a pass); max_ref >= every refID and max_pos >= every pos of the keys: a pass whose digit
+ * is zero in every key of that range is skipped.  tmp: bsdc_zip_sort_tmp_bytes(n) of 8-byte aligned
+ * scratch.  Everything is enqueued on `stream`.  bsdc_zip_sort_host: the same on host pointers.
+ * bsdc_zip_sort_tile: the keys a workgroup handles in a pass.
+ *
+ * bsdc_zip_format: output record k is table entry idx[k]: off [n + 1] receives the exclusive prefix
+ * sum of the records' byte counts and dst + off[k] the record -- the aligned record's bytes up to
+ * its aux (rec + rec_off, aux_start of them) with block_size the output's and flag bit 0x200
+ * replaced by flag_or's; then its aux tags but those whose name the partner's aux (part +
+ * part_off, part_len bytes) also holds and those named in tags->remove; then the partner's tags
+ * but those in tags->remove, and, where the record's flag has 0x10: a Z or B tag named in
+ * tags->reverse with its bytes / elements in reverse order, a Z tag named in tags->revcomp
+ * reversed with A<->T, C<->G in both cases.  Tags are found by walking the aux by type.  No byte
+ * at or past dst + cap is written; bsdc_zip_bytes_bound (of the host table) is a cap that holds.
+ * idx, tab, rec, part, off, dst, tmp (bsdc_zip_format_tmp_bytes(n), 8-byte aligned): device
+ * pointers; tab_host, rec_host, part_host: the caller's host copies, which are what gets checked;
+ * rec and part 4-byte aligned.  BSDC_EINVAL before anything is enqueued, with the reason in
+ * bsdc_zip_last_error (thread-local): a NULL pointer, a negative count, a table entry that leaves
+ * rec / part, a cap below the bound, more than BSDC_ZIP_MAX_TAGS names in a list, and a record one
+ * of whose aux blocks holds a tag of an unknown type or one that runs past the block (the message
+ * names the entry and its read).  bsdc_zip_format_host: host pointers, the same per-record
+ * functions run sequentially on the CPU.
+ *
+ * bsdc_zip_scan_host: the records of `bytes` (BAM records back to back, as they lie behind the
+ * header) listed into out [cap] -> their count (call with out NULL to count), < 0 on a record that
+ * is truncated or whose lengths leave it. */
+#define BSDC_ZIP_MAX_TAGS 32
+typedef struct {
+    int64_t rec_off;   /* the aligned record (its block_size field) in rec */
+    int64_t part_off;  /* the partner's first aux byte in part */
+    int32_t rec_len;   /* block_size + 4 */
+    int32_t aux_start; /* the aligned record's first aux byte, from rec_off */
+    int32_t part_len;  /* the partner's aux bytes */
+    uint32_t flag_or;  /* 0x200 where the partner's flag has it, else 0 */
+} bsdc_zip_rec;
+
+typedef struct {
+    uint8_t reverse[2 * BSDC_ZIP_MAX_TAGS], revcomp[2 * BSDC_ZIP_MAX_TAGS], remove[2 * BSDC_ZIP_MAX_TAGS]; /* two bytes a name */
+    int32_t n_reverse, n_revcomp, n_remove, reserved;
+} bsdc_zip_tags;
+
+typedef struct {
+    int64_t off;      /* the record (its block_size field) in the bytes */
+    int32_t len;      /* block_size + 4 */
+    int32_t aux;      /* its first aux byte, from off */
+    int32_t ref_id, pos;
+    uint16_t flag;
+    uint8_t name_len; /* without the NUL; the name starts at off + 36 */
+    uint8_t reserved0;
+    int32_t reserved;
+} bsdc_zip_src;
+
+int32_t bsdc_zip_sort_tile(void);
+int64_t bsdc_zip_sort_tmp_bytes(int64_t n);
+int32_t bsdc_zip_sort(uint64_t *keys, uint32_t *idx, int64_t n, int32_t max_ref, int32_t max_pos, uint8_t *tmp, void *stream);
+int32_t bsdc_zip_sort_host(uint64_t *keys, uint32_t *idx, int64_t n, int32_t max_ref, int32_t max_pos);
+int64_t bsdc_zip_bytes_bound(const bsdc_zip_rec *tab_host, int64_t n);
+int64_t bsdc_zip_format_tmp_bytes(int64_t n);
+int32_t bsdc_zip_format(const uint32_t *idx, int64_t n, const bsdc_zip_rec *tab, const bsdc_zip_rec *tab_host,
+                        const uint8_t *rec, const uint8_t *rec_host, int64_t rec_bytes, const uint8_t *part,
+                        const uint8_t *part_host, int64_t part_bytes, const bsdc_zip_tags *tags, int64_t *off, uint8_t *dst,
+                        int64_t cap, uint8_t *tmp, void *stream);
+int32_t bsdc_zip_format_host(const uint32_t *idx, int64_t n, const bsdc_zip_rec *tab, const uint8_t *rec, int64_t rec_bytes,
+                             const uint8_t *part, int64_t part_bytes, const bsdc_zip_tags *tags, int64_t *off, uint8_t *dst,
+                             int64_t cap);
+int64_t bsdc_zip_scan_host(const uint8_t *bytes, int64_t n_bytes, bsdc_zip_src *out, int64_t cap);
+const char *bsdc_zip_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif
