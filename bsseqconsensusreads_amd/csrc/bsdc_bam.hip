@@ -13,11 +13,12 @@
 //     bits of xE) and the record's size land in `tmp`, 12 dwords a record;
 //  2-4. the offset scan of bsdc_devtext.h over the families' byte counts -> off[f];
 //  5. k_bam_write: one wavefront per record.  A record starts at any byte, so a lane owns one
-//     ALIGNED dword of the destination at a time, assembles its four bytes in a register and
-//     stores it whole; only a record's first and last partial dword (and a dword that would cross
-//     `cap`) leave as single bytes.  A dword inside QUAL, packed SEQ, a B:s array, ac / bc or
+//     ALIGNED dword of the destination at a time (bsdc_devtext.h store_record), assembles its four
+//     bytes in a register and stores it whole; only a record's first and last partial dword (and a
+//     dword that would cross `cap`) leave as single bytes.  A dword inside QUAL, packed SEQ, a B:s array, ac / bc or
 //     aq / bq is made of aligned source dwords (load4, nt16x4, add33x4); the fixed fields, the
 //     names, the aux, the tag heads and the seams go byte by byte.
+// The rows a / b of a record, the duplex column rule and xE are bsdc_ssrows.h's.
 // xE = (float)sum(err) / (float)sum(depth): exact 64-bit sums, one rounding each in the
 // conversions, an IEEE divide (this file is built without fast-math); the 0 / 0 of a read without
 // depth takes the bits the launcher computed on the host, which are what the host encoder writes.
@@ -27,6 +28,7 @@
 
 #include "../../include/bsdc.h"
 #include "bsdc_devtext.h"
+#include "bsdc_ssrows.h"
 
 namespace {
 
@@ -76,15 +78,10 @@ BSDC_HD int64_t scan_bytes(const BmArgs &A, int64_t f, int) {
 BSDC_HD int64_t *scan_off(const BmArgs &A, int) { return A.off; }
 
 // one single-strand read's rows, cut to the record's length by the caller
-struct Ss {
-    const uint8_t *b, *q, *d8, *e8;
-    const uint16_t *d16, *e16;  // a wide family's exact values (else nullptr)
-};
-BSDC_HD uint32_t ss_d(const Ss &v, int i) { return v.d16 ? (uint32_t)v.d16[i] : (uint32_t)v.d8[i]; }
-BSDC_HD uint32_t ss_e(const Ss &v, int i) { return v.e16 ? (uint32_t)v.e16[i] : (uint32_t)v.e8[i]; }
+using bsdc_ssrows::Row;
 // b when sb, else a, field by field (registers stay registers)
-BSDC_HD Ss ss_pick(bool sb, const Ss &a, const Ss &b) {
-    return Ss{sb ? b.b : a.b, sb ? b.q : a.q, sb ? b.d8 : a.d8, sb ? b.e8 : a.e8, sb ? b.d16 : a.d16, sb ? b.e16 : a.e16};
+BSDC_HD Row ss_pick(bool sb, const Row &a, const Row &b) {
+    return Row{sb ? b.b : a.b, sb ? b.q : a.q, sb ? b.d8 : a.d8, sb ? b.e8 : a.e8, sb ? b.d16 : a.d16, sb ? b.e16 : a.e16};
 }
 // xD, xM and the bits of xE of one read; a record's: the duplex ("c"), "a" and "b" reads'
 struct Trip {
@@ -95,12 +92,9 @@ struct Stats {
 };
 
 // row (f, s) of the single-strand outputs (on: else an empty view, nothing read)
-BSDC_HD Ss bm_view(const BmArgs &A, bool on, int64_t f, int s) {
-    const int64_t at = (4 * f + s) * (int64_t)A.stride;
-    const int32_t w = on && A.ss_wide ? A.ss_wide[f] : -1;
-    const int64_t aw = (4 * (int64_t)(w < 0 ? 0 : w) + s) * (int64_t)A.stride;
-    return Ss{on ? A.ss_base + at : nullptr,  on ? A.ss_qual + at : nullptr, on ? A.ss_depth + at : nullptr,
-              on ? A.ss_err + at : nullptr,   w >= 0 ? A.ss_wdepth + aw : nullptr, w >= 0 ? A.ss_werr + aw : nullptr};
+BSDC_HD Row bm_view(const BmArgs &A, bool on, int64_t f, int s) {
+    if (!on) return Row{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return bsdc_ssrows::row_of(A, f, s, A.ss_wide ? A.ss_wide[f] : -1);
 }
 
 // One record (family f, end e).  Everything here is the same in every lane of its wavefront.
@@ -108,7 +102,7 @@ struct BmRec {
     const uint8_t *nm, *ax, *sq, *ql;
     int nl, al, L, e;
     int tags, kind, two;  // tags: the consensus tags follow; two: the "b" read is present (duplex)
-    Ss a, b;
+    Row a, b;
     int o_seq, o_qual, o_aux, o_tags;  // where the sections start in the record
 };
 
@@ -125,13 +119,11 @@ BSDC_HD BmRec bm_rec(const BmArgs &A, int64_t f, int e) {
     r.e = e;
     r.tags = A.with_tags;
     r.kind = A.kind;
-    // molecular: row e.  duplex: R1 reads sets (0, 3), R2 sets (1, 2); a = AB when it has a read, else BA
-    const bool dup = r.tags && r.kind == 0;
-    const int sa = e, sb = 3 - e;
-    const bool la = dup && A.ss_len[4 * f + sa] > 0, lb = dup && A.ss_len[4 * f + sb] > 0;
-    r.two = la && lb;
-    r.a = bm_view(A, r.tags != 0, f, dup && !la ? sb : sa);
-    r.b = bm_view(A, r.two != 0, f, sb);
+    // (without tags: the molecular selection, which reads nothing)
+    const bsdc_ssrows::End s = bsdc_ssrows::end_rows(r.tags ? r.kind : 1, A.ss_len, f, e);
+    r.two = s.two;
+    r.a = bm_view(A, r.tags != 0, f, s.a);
+    r.b = bm_view(A, s.two, f, s.b);
     r.o_seq = 36 + r.nl + 1;
     r.o_qual = r.o_seq + (r.L + 1) / 2;
     r.o_aux = r.o_qual + r.L;
@@ -218,7 +210,7 @@ BSDC_HD uint32_t tag_byte(const BmRec &r, const Stats &st, int t) {
     }
     const bool sb = t >= bm_strand(r);
     if (sb) t -= bm_strand(r);
-    const Ss v = ss_pick(sb, r.a, r.b);
+    const Row v = ss_pick(sb, r.a, r.b);
     const uint32_t x = sb ? 'b' : 'a';
     if (t < 8 + 2 * L) return arr_byte(x, 'd', v.d8, v.d16, L, t);
     t -= 8 + 2 * L;
@@ -265,7 +257,7 @@ BSDC_HD uint32_t bm_dword(const BmRec &r, const Stats &st, int size, int o_arr, 
         int t = i0 - o_arr;
         const bool sb = r.kind == 0 && t >= bm_strand(r);
         if (sb) t -= bm_strand(r);
-        const Ss v = ss_pick(sb, r.a, r.b);
+        const Row v = ss_pick(sb, r.a, r.b);
         int k = t - 8;
         if (k >= 0 && k + 4 <= 2 * L) return arr_dword(v.d8, v.d16, k);
         k = t - (16 + 2 * L);
@@ -282,36 +274,13 @@ BSDC_HD uint32_t bm_dword(const BmRec &r, const Stats &st, int size, int o_arr, 
     return x;
 }
 
-// wave reductions (64 lanes)
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-    for (int o = 32; o; o >>= 1) {
-        const uint32_t x = (uint32_t)__shfl_xor((int)v, o);
-        v = x > v ? x : v;
-    }
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-    for (int o = 32; o; o >>= 1) {
-        const uint32_t x = (uint32_t)__shfl_xor((int)v, o);
-        v = x < v ? x : v;
-    }
-    return v;
-}
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-    for (int o = 32; o; o >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o);
-        v += (uint64_t)hi << 32 | lo;
-    }
-    return v;
-}
-
 // D, M, the bits of E of one read from its lanes' partial results
 __device__ __forceinline__ Trip read_stats(uint32_t mx, uint32_t mn, uint64_t sd, uint64_t se, int L, uint32_t nan_bits) {
     mx = wave_max(mx);
     mn = wave_min(mn);
     sd = wave_sum(sd);
     se = wave_sum(se);
-    const float q = (float)(int64_t)se / (float)(int64_t)sd;
+    const float q = bsdc_ssrows::read_rate((int64_t)se, (int64_t)sd);
     return Trip{mx, L ? mn : 0u, (sd == 0 && se == 0) ? nan_bits : __float_as_uint(q)};
 }
 
@@ -333,24 +302,21 @@ __global__ __launch_bounds__(kT) void k_bam_sizes(BmArgs A) {
         uint32_t cmx = 0, cmn = 0xffffffffu, amx = 0, amn = 0xffffffffu, bmx = 0, bmn = 0xffffffffu;
         uint64_t csd = 0, cse = 0, asd = 0, ase = 0, bsd = 0, bse = 0;
         for (int i = lane; i < r.L; i += 64) {
-            const uint32_t ad = ss_d(r.a, i), ae = ss_e(r.a, i);
+            const uint32_t ad = r.a.d(i), ae = r.a.e(i);
             amx = ad > amx ? ad : amx;
             amn = ad < amn ? ad : amn;
             asd += ad;
             ase += ae;
             uint32_t cd = ad, ce = ae;
             if (r.two) {
-                const uint32_t bd = ss_d(r.b, i), be = ss_e(r.b, i);
+                const uint32_t bd = r.b.d(i), be = r.b.e(i);
                 bmx = bd > bmx ? bd : bmx;
                 bmn = bd < bmn ? bd : bmn;
                 bsd += bd;
                 bse += be;
-                // the duplex call before its N mask; errors counted against it: a strand whose call
-                // agrees contributes its errors, one that disagrees all of its reads
-                const uint32_t ab = r.a.b[i] & 15u, bb = r.b.b[i] & 15u, aq = r.a.q[i], bq = r.b.q[i];
-                const uint32_t raw = ab == bb ? ab : aq > bq ? ab : bq > aq ? bb : ab;
-                cd = ad + bd;
-                ce = (ab == raw ? ae : ad) + (bb == raw ? be : bd);
+                const bsdc_ssrows::Col c = bsdc_ssrows::duplex_col(r.a.b[i], r.a.q[i], ad, ae, r.b.b[i], r.b.q[i], bd, be);
+                cd = c.d;
+                ce = c.e;
             }
             cmx = cd > cmx ? cd : cmx;
             cmn = cd < cmn ? cd : cmn;
@@ -383,21 +349,7 @@ __global__ __launch_bounds__(kT) void k_bam_write(BmArgs A) {
     const BmRec r = bm_rec(A, f, e);
     const int o_arr = r.o_tags + (r.tags ? bm_trips(r, st) : 0);
     const int64_t o = A.off[f] + (e ? (int64_t)A.stat[(2 * f) * kStat] : 0);
-    uint8_t *base = A.rec;
-    const int ho = (int)((uintptr_t)(base + o) & 3u);
-    const int nd = (ho + size + 3) >> 2;
-    for (int k = threadIdx.x & 63; k < nd; k += 64) {
-        // dword k covers the record's bytes 4k - ho ..; ho = the start's offset in its dword
-        const int i0 = 4 * k - ho;
-        const uint32_t v = bm_dword(r, st, size, o_arr, i0);
-        const int64_t p = o + i0;
-        if (i0 >= 0 && i0 + 4 <= size && p + 4 <= A.cap) {
-            *reinterpret_cast<uint32_t *>(base + p) = v;
-            continue;
-        }
-        for (int b = 0; b < 4; b++)
-            if (i0 + b >= 0 && i0 + b < size && p + b < A.cap) base[p + b] = (uint8_t)(v >> (8 * b));
-    }
+    store_record(A.rec, o, size, A.cap, threadIdx.x & 63, 64, [&](int i0) { return bm_dword(r, st, size, o_arr, i0); });
 }
 
 int64_t groups_of(int64_t n_fam) { return (n_fam + kFamPerGroup - 1) / kFamPerGroup; }

@@ -1,7 +1,11 @@
-// What the device-side output formatters (bsdc_fastq.hip, bsdc_bam.hip) share: the three-launch
-// offset scan over the families' byte counts and the dword helpers of the "a lane owns one aligned
-// destination dword" writers.  Everything here is a template or inline: each including file
-// instantiates its own copy.
+// What the passes over the vote's outputs share (bsdc_fastq.hip, bsdc_bam.hip, bsdc_toolrec.hip,
+// bsdc_zipper.hip; the macro also bsdc_image.hip, bsdc_metrics.hip, bsdc_filter.hip and
+// bsdc_ssrows.h).  Everything here is a template or inline: each including file instantiates its
+// own copy.
+//
+// The upper half is plain C++ and compiles under g++ (the host twins and libbsdc_io include it):
+// BSDC_HD, the dword helpers and the "a lane owns one aligned destination dword" record writer.
+// The lower half is hipcc's alone: the 64-lane wave reductions and the three-launch offset scan.
 //
 // The scan, over an argument record A of the including file (passed by value to the kernels):
 //   A.n_fam, A.groups = ceil(n_fam / kFamPerGroup), A.bsum [D][groups + 1] int64 scratch,
@@ -12,10 +16,15 @@
 //  3. k_scan_off<D>: each workgroup scans its families' counts again from its base -> off[d][f].
 #ifndef BSDC_DEVTEXT_H
 #define BSDC_DEVTEXT_H
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
 #define BSDC_HD __host__ __device__ __forceinline__
+#else
+#define BSDC_HD inline
+#endif
 
 namespace bsdc_devtext {
 
@@ -44,14 +53,74 @@ BSDC_HD uint32_t nt16x4(uint32_t c) {
 BSDC_HD uint32_t add33x4(uint32_t x) { return ((x & 0x7f7f7f7fu) + 0x21212121u) ^ (x & 0x80808080u); }
 
 // bytes a[0..3] as one little-endian dword by two aligned loads and a funnel shift.  The aligned
-// dwords that hold a[0] and a[3] are read: the caller keeps both inside the source row (a row that
-// starts 4-byte aligned, is a multiple of 4 long and holds a[0..3]).
+// dwords that hold a[0] and a[3] are read: the caller keeps both inside the source buffer (can4, or
+// a row that starts 4-byte aligned, is a multiple of 4 long and holds a[0..3]).
 BSDC_HD uint32_t load4(const uint8_t *a) {
     const int sh = (int)((uintptr_t)a & 3u);
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(a - sh);
-    uint32_t x = w[0];
-    if (sh) x = (x >> (8 * sh)) | (w[1] << (32 - 8 * sh));
-    return x;
+    uint32_t x, y;
+    memcpy(&x, __builtin_assume_aligned(a - sh, 4), 4);
+    if (!sh) return x;
+    memcpy(&y, __builtin_assume_aligned(a - sh + 4, 4), 4);
+    return (x >> (8 * sh)) | (y << (32 - 8 * sh));
+}
+// a[0..3] is inside [buf, buf + n) with the aligned dwords that hold a[0] and a[3] (buf 4-byte aligned)
+BSDC_HD bool can4(const uint8_t *buf, int64_t n, const uint8_t *a) {
+    return a >= buf && (int64_t)((a + 3 - buf) | 3) < n;
+}
+
+// The record writer: a record of `size` bytes starts at base + o, at any byte, and `cap` bytes of
+// base are writable.  A lane (lane, lane + nlanes, ..) owns one ALIGNED dword of the destination at
+// a time: dword k covers the record's bytes i0 = 4k - ho .., ho = the start's offset in its dword;
+// dword_of(i0) gives bytes i0 .. i0 + 3 of the record (whatever it likes outside [0, size)).  A
+// dword inside the record and below cap is stored whole, else the bytes inside both.
+template <class F>
+BSDC_HD void store_record(uint8_t *base, int64_t o, int size, int64_t cap, int lane, int nlanes, F dword_of) {
+    const int ho = (int)((uintptr_t)(base + o) & 3u);
+    const int nd = (ho + size + 3) >> 2;
+    for (int k = lane; k < nd; k += nlanes) {
+        const int i0 = 4 * k - ho;
+        const uint32_t v = dword_of(i0);
+        const int64_t p = o + i0;
+        if (i0 >= 0 && i0 + 4 <= size && p + 4 <= cap) {
+            memcpy(__builtin_assume_aligned(base + p, 4), &v, 4);  // (aligned: one dword store)
+            continue;
+        }
+        for (int b = 0; b < 4; b++)
+            if (i0 + b >= 0 && i0 + b < size && p + b < cap) base[p + b] = (uint8_t)(v >> (8 * b));
+    }
+}
+
+#ifdef __HIPCC__
+// wave reductions (64 lanes): every lane gets the result
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
+    return v;
+}
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
+        v += (uint64_t)hi << 32 | lo;
+    }
+    return v;
+}
+__device__ __forceinline__ int64_t wave_sum(int64_t v) { return (int64_t)wave_sum((uint64_t)v); }
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        const uint32_t x = (uint32_t)__shfl_xor((int)v, m, 64);
+        v = x > v ? x : v;
+    }
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        const uint32_t x = (uint32_t)__shfl_xor((int)v, m, 64);
+        v = x < v ? x : v;
+    }
+    return v;
 }
 
 // exclusive scan of one value per thread over the workgroup (sh: 2 * kT values); *total = the sum
@@ -130,6 +199,8 @@ inline void launch_scan(const Args &A, hipStream_t st) {
     hipLaunchKernelGGL((k_scan_scan<D, Args>), dim3(1), dim3(kT), 0, st, A);
     if (A.groups) hipLaunchKernelGGL((k_scan_off<D, Args>), dim3((unsigned)A.groups), dim3(kT), 0, st, A);
 }
+
+#endif  // __HIPCC__
 
 }  // namespace bsdc_devtext
 #endif

@@ -8,13 +8,13 @@
 //  1-3. the offset scan of bsdc_devtext.h (k_scan_sum / k_scan_scan / k_scan_off, shared with
 //     bsdc_bam.hip) over the families' byte counts per file -> off[d][f], off[d][n_fam] = the total;
 //  4. k_fq_text: one wavefront per (family, end).  A record starts at any byte of the text, so a
-//     lane owns one ALIGNED dword of the destination at a time: it assembles the dword's four
-//     bytes in a register and stores it whole; only a record's first and last partial dword (and
-//     a dword that would cross `cap`) leave as single bytes.  A dword inside SEQ takes its four
-//     nt16 codes from two or three packed bytes and maps them through a 16-byte register table
-//     with v_perm_b32; a dword inside QUAL is an unaligned dword of the quality row (two aligned
-//     loads, funnel shift) plus 33 in every byte, no carry between bytes; the name, the separators
-//     and the seams go byte by byte.
+//     lane owns one ALIGNED dword of the destination at a time (bsdc_devtext.h store_record): it
+//     assembles the dword's four bytes in a register and stores it whole; only a record's first
+//     and last partial dword (and a dword that would cross `cap`) leave as single bytes.  A dword
+//     inside SEQ takes its four nt16 codes from two or three packed bytes and maps them through a
+//     16-byte register table with v_perm_b32; a dword inside QUAL is an unaligned dword of the
+//     quality row (load4: two aligned loads, funnel shift) plus 33 in every byte, no carry between
+//     bytes; the name, the separators and the seams go byte by byte.
 // bsdc_bgzf_crc32: one 256-thread workgroup per block.  The block is staged in LDS (16-byte
 // loads), thread t runs the raw CRC (register 0, no final xor) over segment t of 255 bytes by
 // slice-by-4 (tables in LDS, 4 KB), multiplies it by x^(8 * 255 * (255 - t)) mod P -- the raw CRC
@@ -29,7 +29,7 @@
 
 namespace {
 
-using namespace bsdc_devtext;  // kT, kFamPerGroup, nt16x4, the scan
+using namespace bsdc_devtext;  // kT, kFamPerGroup, nt16x4, load4, store_record, the scan
 
 constexpr int kSeg = 255;  // bytes per thread segment of a BGZF block (bsdc_bgzf.hip's segmentation)
 constexpr int kBlock = kT * kSeg;
@@ -174,14 +174,8 @@ BSDC_HD uint32_t fq_byte(const FqRec &r, int i) {
 // bytes i0 .. i0 + 3 of the record as one little-endian dword (bytes outside the record: 0)
 BSDC_HD uint32_t fq_dword(const FqRec &r, int i0) {
     const int s0 = r.nl + 4, q0 = r.nl + 7 + r.L;
-    if (i0 >= q0 && i0 + 4 <= q0 + r.L) {  // inside QUAL: an unaligned dword of the row, + 33 per byte
-        const uint8_t *a = r.ql + (i0 - q0);
-        const int sh = (int)((uintptr_t)a & 3u);
-        const uint32_t *w = reinterpret_cast<const uint32_t *>(a - sh);
-        uint32_t x = w[0];
-        if (sh) x = (x >> (8 * sh)) | (w[1] << (32 - 8 * sh));  // (w[1] holds a byte of the four: inside the row)
-        return ((x & 0x7f7f7f7fu) + 0x21212121u) ^ (x & 0x80808080u);
-    }
+    // inside QUAL: an unaligned dword of the row (its second aligned dword holds a byte of the four), + 33 per byte
+    if (i0 >= q0 && i0 + 4 <= q0 + r.L) return add33x4(load4(r.ql + (i0 - q0)));
     if (i0 >= s0 && i0 + 4 <= s0 + r.L) {  // inside SEQ: codes j .. j + 3 of the packed row, high nibble first
         const int j = i0 - s0, s = j & 1;
         const uint8_t *a = r.sq + (j >> 1);
@@ -193,20 +187,6 @@ BSDC_HD uint32_t fq_dword(const FqRec &r, int i0) {
     uint32_t v = 0;
     for (int b = 0; b < 4; b++) v |= fq_byte(r, i0 + b) << (8 * b);
     return v;
-}
-
-// The stores of dword k of a record that starts at text byte o (the text at base, cap bytes of it
-// writable): dword k covers the record's bytes 4k - ho .., ho = the start's offset in its dword.
-BSDC_HD void fq_store(const FqRec &r, uint8_t *base, int64_t o, int64_t cap, int ho, int k) {
-    const int i0 = 4 * k - ho;
-    const uint32_t v = fq_dword(r, i0);
-    const int64_t p = o + i0;
-    if (i0 >= 0 && i0 + 4 <= r.size && p + 4 <= cap) {
-        *reinterpret_cast<uint32_t *>(base + p) = v;
-        return;
-    }
-    for (int b = 0; b < 4; b++)
-        if (i0 + b >= 0 && i0 + b < r.size && p + b < cap) base[p + b] = (uint8_t)(v >> (8 * b));
 }
 
 BSDC_HD FqRec fq_rec(const FqArgs &A, int64_t f, int d) {
@@ -230,11 +210,7 @@ __global__ __launch_bounds__(kT) void k_fq_text(FqArgs A) {
     const int d = (int)(w & 1);
     if (f >= A.n_fam || !fq_kept(A, f)) return;
     const FqRec r = fq_rec(A, f, d);
-    const int64_t o = A.off[d][f];
-    uint8_t *base = A.text[d];
-    const int ho = (int)((uintptr_t)(base + o) & 3u);
-    const int nd = (ho + r.size + 3) >> 2;
-    for (int k = threadIdx.x & 63; k < nd; k += 64) fq_store(r, base, o, A.cap[d], ho, k);
+    store_record(A.text[d], A.off[d][f], r.size, A.cap[d], threadIdx.x & 63, 64, [r](int i0) { return fq_dword(r, i0); });
 }
 
 }  // namespace

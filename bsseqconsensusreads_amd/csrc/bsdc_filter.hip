@@ -11,7 +11,8 @@
 // the read's length ride along unchanged).  Two sweeps per end: the per-read sums and maxima of the
 // read-level gate (integer wave reductions by __shfl_xor), then, for an end that passed, the
 // per-base mask with the no-call and mean-quality counts; the second sweep finds its rows in L2.
-// Rates: the per-read ones are float32 divides (the tag encoder's, bsdc_io.cpp per_read; hipcc's
+// The rows a / b of an end, the duplex column rule and the per-read rate are bsdc_ssrows.h's.
+// Rates: the per-read ones are float32 divides (the tag encoder's, bsdc_ssrows.h read_rate; hipcc's
 // default correctly rounded divide), the per-base ones fp64 divides, both compared in fp64.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -19,6 +20,8 @@
 #include <string>
 
 #include "../../include/bsdc.h"
+#include "bsdc_devtext.h"
+#include "bsdc_ssrows.h"
 
 namespace bsdc_internal {  // csrc/bsdc_kernels.hip: the context's device and error text
 int ctx_device(const bsdc_ctx *c);
@@ -46,23 +49,9 @@ struct FilterArgs {
     uint16_t *masked;
 };
 
-// one single-strand row (f, s): bases, qualities, and the depths / errors as bytes or, for a family
-// with a wide row, as its exact u16 values (bsdc_io.cpp SsView)
-struct Row {
-    const uint8_t *b, *q, *d8, *e8;
-    const uint16_t *d16, *e16;
-};
-
-__device__ inline Row row_of(const FilterArgs &A, int64_t f, int s, int32_t wide) {
-    const size_t at = (size_t)(4 * f + s) * (size_t)A.stride;
-    Row r{A.ss_base + at, A.ss_qual + at, A.ss_depth + at, A.ss_err + at, nullptr, nullptr};
-    if (wide >= 0) {
-        const size_t aw = (size_t)(4 * (int64_t)wide + s) * (size_t)A.stride;
-        r.d16 = A.ss_wdepth + aw;
-        r.e16 = A.ss_werr + aw;
-    }
-    return r;
-}
+using bsdc_devtext::wave_max;
+using bsdc_devtext::wave_sum;
+using bsdc_ssrows::Row;  // one single-strand row (f, s)
 
 // the lane's 8 columns from c0 (a multiple of 8) of a byte row / a u16 row
 __device__ inline void load8(const uint8_t *p, int c0, uint32_t v[kCols]) {
@@ -88,17 +77,6 @@ __device__ inline void load_counts(const Row &r, int c0, uint32_t d[kCols], uint
     }
 }
 
-__device__ inline uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
-    return v;
-}
-__device__ inline uint32_t wave_max(uint32_t v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, m, 64));
-    return v;
-}
-
 __device__ inline double rate64(uint32_t e, uint32_t d) { return d ? (double)e / (double)d : 0.0; }
 __device__ inline float nan0(float x) { return x != x ? 0.0f : x; }
 
@@ -107,15 +85,9 @@ __device__ int filter_end(const FilterArgs &A, int64_t f, int e, int lane, uint3
     const bsdc_filter_params &p = A.p;
     const int L = min((int)A.len[2 * f + e], A.stride);
     const int32_t wide = A.ss_wide ? A.ss_wide[f] : -1;
-    // strand rows (0, 3) for R1 and (1, 2) for R2; a = the AB row or the only one present
-    bool two = false;
-    int sa = e, sb = 3 - e;
-    if (A.kind == 0) {
-        const bool la = A.ss_len[4 * f + sa] > 0, lb = A.ss_len[4 * f + sb] > 0;
-        two = la && lb;
-        if (!la) sa = sb;
-    }
-    const Row a = row_of(A, f, sa, wide), b = row_of(A, f, sb, wide);
+    const bsdc_ssrows::End s = bsdc_ssrows::end_rows(A.kind, A.ss_len, f, e);
+    const bool two = s.two;
+    const Row a = bsdc_ssrows::row_of(A, f, s.a, wide), b = bsdc_ssrows::row_of(A, f, s.b, wide);
 
     // sweep 1: the per-read depths and error sums (all below 2^32: L <= 65535, counts <= 32767)
     uint32_t sad = 0, sae = 0, sbd = 0, sbe = 0, std_ = 0, ste = 0, mad = 0, mbd = 0, mcd = 0;
@@ -139,13 +111,10 @@ __device__ int filter_end(const FilterArgs &A, int64_t f, int e, int lane, uint3
                 sbd += bd[j];
                 sbe += be[j];
                 mbd = max(mbd, bd[j]);
-                // the duplex call before its N mask; a strand whose call agrees with it contributes
-                // its errors, one that disagrees all of its reads (bsdc_io.cpp te)
-                const uint32_t x = ab[j] & 15u, y = bb[j] & 15u;
-                const uint32_t raw = x == y ? x : aq[j] > bq[j] ? x : bq[j] > aq[j] ? y : x;
-                std_ += ad[j] + bd[j];
-                ste += (x == raw ? ae[j] : ad[j]) + (y == raw ? be[j] : bd[j]);
-                mcd = max(mcd, ad[j] + bd[j]);
+                const bsdc_ssrows::Col c = bsdc_ssrows::duplex_col(ab[j], aq[j], ad[j], ae[j], bb[j], bq[j], bd[j], be[j]);
+                std_ += c.d;
+                ste += c.e;
+                mcd = max(mcd, c.d);
             }
         }
     }
@@ -157,8 +126,9 @@ __device__ int filter_end(const FilterArgs &A, int64_t f, int e, int lane, uint3
         std_ = sad, ste = sae, mcd = mad;
     }
     // the read-level gate (a NaN rate, no depth at all, never exceeds a threshold)
-    const float aE = (float)sae / (float)sad, cE = (float)ste / (float)std_;
-    const float bE = two ? (float)sbe / (float)sbd : 0.0f;
+    using bsdc_ssrows::read_rate;
+    const float aE = read_rate(sae, sad), cE = read_rate(ste, std_);
+    const float bE = two ? read_rate(sbe, sbd) : 0.0f;
     int reason = 0;
     if ((int64_t)mcd < (int64_t)p.min_reads[0]) reason |= BSDC_FILT_MINREADS;
     if ((double)cE > p.max_read_error_rate[0]) reason |= BSDC_FILT_READERR;

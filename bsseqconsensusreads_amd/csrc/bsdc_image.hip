@@ -28,16 +28,13 @@
 #include <string>
 
 #include "../../include/bsdc.h"
+#include "bsdc_devtext.h"  // BSDC_HD
 
 #ifdef __HIPCC__
-#include <hip/hip_runtime.h>
-#define IMG_HD __host__ __device__ __forceinline__
 namespace bsdc_internal {  // csrc/bsdc_kernels.hip: the context's device and error text
 int ctx_device(const bsdc_ctx *c);
 int32_t ctx_fail(bsdc_ctx *c, int32_t code, const std::string &msg);
 }  // namespace bsdc_internal
-#else
-#define IMG_HD inline
 #endif
 
 namespace {
@@ -56,7 +53,7 @@ struct ImgArgs {
 };
 
 // 0, or which field of the entry is out of range: 1 src, 2 skip + len, 3 slot % 4, 4 slot
-IMG_HD int img_rec_check(const bsdc_image_rec &r, int64_t n_raw, int64_t n_slots) {
+BSDC_HD int img_rec_check(const bsdc_image_rec &r, int64_t n_raw, int64_t n_slots) {
     if (r.src < 0 || r.l_seq < 0 || r.src > n_raw || ((int64_t)r.l_seq + 1) / 2 + r.l_seq > n_raw - r.src) return 1;
     if (r.skip < 0 || r.len < 0 || (int64_t)r.skip + r.len > r.l_seq) return 2;
     if (r.slot & 3u) return 3;
@@ -65,7 +62,7 @@ IMG_HD int img_rec_check(const bsdc_image_rec &r, int64_t n_raw, int64_t n_slots
 }
 
 // aligned dword a of raw, little-endian; bytes outside [0, n_raw) read as 0
-IMG_HD uint32_t img_ld(const uint8_t *raw, int64_t n_raw, int64_t a) {
+BSDC_HD uint32_t img_ld(const uint8_t *raw, int64_t n_raw, int64_t a) {
     const int64_t o = 4 * a;
     if (a < 0 || o >= n_raw) return 0;
     if (o + 4 <= n_raw) return *reinterpret_cast<const uint32_t *>(raw + o);
@@ -75,13 +72,13 @@ IMG_HD uint32_t img_ld(const uint8_t *raw, int64_t n_raw, int64_t a) {
 }
 
 // dwords of the qual image / the packed image that hold bases of the record
-IMG_HD int64_t img_nq(const bsdc_image_rec &r) { return r.len > 0 ? r.len / 4 + 1 : 0; }
-IMG_HD int64_t img_ns(const bsdc_image_rec &r) {
+BSDC_HD int64_t img_nq(const bsdc_image_rec &r) { return r.len > 0 ? r.len / 4 + 1 : 0; }
+BSDC_HD int64_t img_ns(const bsdc_image_rec &r) {
     return r.len > 0 ? (((int64_t)r.slot + r.len) >> 3) - ((int64_t)r.slot >> 3) + 1 : 0;
 }
 
 // qual dword k of the record: image bytes slot + 4k .. slot + 4k + 3, byte b = qual 4k + b - 1
-IMG_HD void img_qual(const ImgArgs &A, const bsdc_image_rec &r, int64_t k) {
+BSDC_HD void img_qual(const ImgArgs &A, const bsdc_image_rec &r, int64_t k) {
     const int64_t D = ((int64_t)r.slot >> 2) + k;
     if (D >= (A.n_slots >> 2)) return;
     const int64_t P = r.src + ((int64_t)r.l_seq + 1) / 2 + r.skip + 4 * k - 1;  // source byte of image byte 4D
@@ -98,7 +95,7 @@ IMG_HD void img_qual(const ImgArgs &A, const bsdc_image_rec &r, int64_t k) {
 
 // seq dword k of the record: image nibbles 8D .. 8D + 7 (D = slot / 8 + k), nibble n = base
 // 8D + n - slot - 1; stored whole when both 4-nibble halves lie in the record's slot
-IMG_HD void img_seq(const ImgArgs &A, const bsdc_image_rec &r, int64_t k) {
+BSDC_HD void img_seq(const ImgArgs &A, const bsdc_image_rec &r, int64_t k) {
     const int64_t S = r.slot, D = (S >> 3) + k;
     if (D >= (A.n_slots >> 3)) return;
     const int64_t P = 2 * r.src + r.skip + 8 * D - S - 1;  // source nibble of image nibble 8D
@@ -122,7 +119,7 @@ IMG_HD void img_seq(const ImgArgs &A, const bsdc_image_rec &r, int64_t k) {
 }
 
 // item t of the record: its qual dwords, then its seq dwords
-IMG_HD void img_item(const ImgArgs &A, const bsdc_image_rec &r, int64_t t, int64_t nq) {
+BSDC_HD void img_item(const ImgArgs &A, const bsdc_image_rec &r, int64_t t, int64_t nq) {
     if (t < nq)
         img_qual(A, r, t);
     else

@@ -8,6 +8,7 @@
 // Writer: record sizes -> prefix sums -> parallel encode into one buffer -> 0xff00-byte BGZF
 // blocks deflated in parallel -> one write, then the 28-byte EOF block.
 #include "../../include/bsdc_io.h"
+#include "bsdc_ssrows.h"
 
 #include <dlfcn.h>
 #include <zlib.h>
@@ -2682,16 +2683,6 @@ struct AuxOut {
     }
 };
 
-struct SsView {  // one single-strand consensus read, truncated to `len`: depths / errors as the
-                 // kernels' bytes, or a wide family's exact u16 values (w16 set)
-    const uint8_t *b, *q;
-    const uint8_t *d8, *e8;
-    const uint16_t *d16, *e16;
-    int32_t len;
-    int64_t d(int32_t i) const { return d16 ? (int64_t)d16[i] : (int64_t)d8[i]; }
-    int64_t e(int32_t i) const { return e16 ? (int64_t)e16[i] : (int64_t)e8[i]; }
-};
-
 // D (max depth), M (min depth), E (errors / depth) of one read; depth(i), err(i) per column
 template <class Dep, class Err>
 void per_read(AuxOut &o, const char *tD, const char *tM, const char *tE, Dep depth, Err err, int32_t len) {
@@ -2705,7 +2696,7 @@ void per_read(AuxOut &o, const char *tD, const char *tM, const char *tE, Dep dep
     }
     o.integer(tD, mx);
     o.integer(tM, mn);
-    o.real(tE, (float)se / (float)sd);
+    o.real(tE, bsdc_ssrows::read_rate(se, sd));
 }
 
 // a B:s array of the kernels' counts: a wide family's u16 values as they are (the same 16 bits as
@@ -2734,21 +2725,18 @@ extern "C" int64_t bsdc_consensus_tags(int64_t n, const int64_t *row_a, const in
                                        const uint16_t *ss_wdepth, const uint16_t *ss_werr, int64_t *off, uint8_t *buf,
                                        int32_t n_threads) {
     set_threads(n_threads);
+    struct {  // (what bsdc_ssrows::row_of reads)
+        const uint8_t *ss_base, *ss_qual, *ss_depth, *ss_err;
+        const uint16_t *ss_wdepth, *ss_werr;
+        int32_t stride;
+    } const rows{ss_base, ss_qual, ss_depth, ss_err, ss_wdepth, ss_werr, stride};
     auto one = [&](int64_t k, uint8_t *p) -> int64_t {
         AuxOut o{p};
         const int32_t L = out_len[k];
-        auto view = [&](int64_t row) {
-            const size_t at = (size_t)row * (size_t)stride;
-            SsView v{ss_base + at, ss_qual + at, ss_depth + at, ss_err + at, nullptr, nullptr, L};
-            const int32_t w = ss_wide ? ss_wide[row >> 2] : -1;
-            if (w >= 0) {
-                const size_t aw = (4 * (size_t)w + (size_t)(row & 3)) * (size_t)stride;
-                v.d16 = ss_wdepth + aw;
-                v.e16 = ss_werr + aw;
-            }
-            return v;
+        auto view = [&](int64_t row) {  // row = 4 f + s
+            return bsdc_ssrows::row_of(rows, row >> 2, (int)(row & 3), ss_wide ? ss_wide[row >> 2] : -1);
         };
-        const SsView a = view(row_a[k]);
+        const bsdc_ssrows::Row a = view(row_a[k]);
         auto ad = [&](int32_t i) { return a.d(i); };
         auto ae = [&](int32_t i) { return a.e(i); };
         if (kind == 1) {  // molecular: cD cM cE, cd ce
@@ -2758,16 +2746,13 @@ extern "C" int64_t bsdc_consensus_tags(int64_t n, const int64_t *row_a, const in
             return o.n;
         }
         const bool two = row_b[k] >= 0;
-        const SsView b = two ? view(row_b[k]) : SsView{};
+        const bsdc_ssrows::Row b = two ? view(row_b[k]) : bsdc_ssrows::Row{};
         if (two) {
-            // the duplex call before its N mask; errors counted against it: a strand whose call
-            // agrees contributes its errors, one that disagrees all of its reads
-            auto td = [&](int32_t i) { return a.d(i) + b.d(i); };
-            auto te = [&](int32_t i) {
-                const uint8_t ab = a.b[i] & 15, bb = b.b[i] & 15;
-                const uint8_t raw = ab == bb ? ab : a.q[i] > b.q[i] ? ab : b.q[i] > a.q[i] ? bb : ab;
-                return (ab == raw ? a.e(i) : a.d(i)) + (bb == raw ? b.e(i) : b.d(i));
+            auto col = [&](int32_t i) {
+                return bsdc_ssrows::duplex_col(a.b[i], a.q[i], a.d(i), a.e(i), b.b[i], b.q[i], b.d(i), b.e(i));
             };
+            auto td = [&](int32_t i) { return col(i).d; };
+            auto te = [&](int32_t i) { return col(i).e; };
             per_read(o, "cD", "cM", "cE", td, te, L);
         } else {
             per_read(o, "cD", "cM", "cE", ad, ae, L);

@@ -5,7 +5,8 @@
 // consensus tags that a user picks the filter's thresholds from, with no tag byte copied out.
 //
 // A fixed number of 256-thread workgroups strides over the families, one wavefront per family, its
-// two ends in turn (the views a / b are the filter's and the tag encoder's).  A lane
+// two ends in turn (the views a / b and the per-read rate are bsdc_ssrows.h's; its
+// duplex column rule is written out in met_record, for the kernel's speed).  A lane
 // owns 4 consecutive columns per round of 256: one dword per byte row, two per u16 wide row, one
 // 16-bit word of packed seq, one dword of qual (strides are multiples of 16, rows 16-byte aligned).
 // All tables live in LDS as u32, added to with LDS atomics: the three histograms, and by_cycle
@@ -27,17 +28,16 @@
 #include <string>
 
 #include "../../include/bsdc.h"
+#include "bsdc_devtext.h"
+#include "bsdc_ssrows.h"
 
 #ifdef __HIPCC__
-#include <hip/hip_runtime.h>
-#define MET_HD __host__ __device__ __forceinline__
 #define MET_UNROLL _Pragma("unroll")
 namespace bsdc_internal {  // csrc/bsdc_kernels.hip: the context's device and error text
 int ctx_device(const bsdc_ctx *c);
 int32_t ctx_fail(bsdc_ctx *c, int32_t code, const std::string &msg);
 }  // namespace bsdc_internal
 #else
-#define MET_HD inline
 #define MET_UNROLL
 #endif
 
@@ -67,24 +67,10 @@ struct MetArgs {
     const uint16_t *ss_wdepth, *ss_werr;
 };
 
-struct MetRow {
-    const uint8_t *b, *q, *d8, *e8;
-    const uint16_t *d16, *e16;
-};
-
-MET_HD MetRow met_row(const MetArgs &A, int64_t f, int s, int32_t wide) {
-    const size_t at = (size_t)(4 * f + s) * (size_t)A.stride;
-    MetRow r{A.ss_base + at, A.ss_qual + at, A.ss_depth + at, A.ss_err + at, nullptr, nullptr};
-    if (wide >= 0) {
-        const size_t aw = (size_t)(4 * (int64_t)wide + s) * (size_t)A.stride;
-        r.d16 = A.ss_wdepth + aw;
-        r.e16 = A.ss_werr + aw;
-    }
-    return r;
-}
+using bsdc_ssrows::Row;  // one single-strand row (f, s)
 
 // aligned little-endian loads (the twin copies: no alignment assumed of a host caller's casts)
-MET_HD uint32_t met_ld32(const void *p) {
+BSDC_HD uint32_t met_ld32(const void *p) {
 #ifdef __HIP_DEVICE_COMPILE__
     return *reinterpret_cast<const uint32_t *>(p);
 #else
@@ -93,7 +79,7 @@ MET_HD uint32_t met_ld32(const void *p) {
     return v;
 #endif
 }
-MET_HD uint32_t met_ld16(const void *p) {
+BSDC_HD uint32_t met_ld16(const void *p) {
 #ifdef __HIP_DEVICE_COMPILE__
     return *reinterpret_cast<const uint16_t *>(p);
 #else
@@ -104,11 +90,11 @@ MET_HD uint32_t met_ld16(const void *p) {
 }
 
 // the lane's 4 columns from c0 (a multiple of 4) of a byte row / of the depths and errors
-MET_HD void met_ld4(const uint8_t *p, int c0, uint32_t v[kMetCols]) {
+BSDC_HD void met_ld4(const uint8_t *p, int c0, uint32_t v[kMetCols]) {
     const uint32_t w = met_ld32(p + c0);
     v[0] = w & 255u, v[1] = (w >> 8) & 255u, v[2] = (w >> 16) & 255u, v[3] = w >> 24;
 }
-MET_HD void met_counts(const MetRow &r, int c0, uint32_t d[kMetCols], uint32_t e[kMetCols]) {
+BSDC_HD void met_counts(const Row &r, int c0, uint32_t d[kMetCols], uint32_t e[kMetCols]) {
     if (r.d16) {
         const uint32_t d0 = met_ld32(r.d16 + c0), d1 = met_ld32(r.d16 + c0 + 2);
         const uint32_t e0 = met_ld32(r.e16 + c0), e1 = met_ld32(r.e16 + c0 + 2);
@@ -121,16 +107,16 @@ MET_HD void met_counts(const MetRow &r, int c0, uint32_t d[kMetCols], uint32_t e
 }
 
 // bin of a per-read error rate: floor(x * 1000) capped at 100 (an infinite rate too), NaN -> 101
-MET_HD int met_rate_bin(float x) {
+BSDC_HD int met_rate_bin(float x) {
     if (x != x) return 101;
     const double t = (double)x * 1000.0;
     return t >= 100.0 ? 100 : (int)floor(t);
 }
 
-MET_HD bool met_acgt(uint32_t x) { return x == 1u || x == 2u || x == 4u || x == 8u; }
+BSDC_HD bool met_acgt(uint32_t x) { return x == 1u || x == 2u || x == 4u || x == 8u; }
 
 // 0, or why family f is skipped: 1 a length beyond the stride, 2 a wide row outside the table
-MET_HD int met_family_check(const MetArgs &A, int64_t f, int32_t *wide) {
+BSDC_HD int met_family_check(const MetArgs &A, int64_t f, int32_t *wide) {
     *wide = A.ss_wide ? A.ss_wide[f] : -1;
     if ((int)A.len[2 * f] > A.stride || (int)A.len[2 * f + 1] > A.stride) return 1;
     if (*wide >= 0 && (int64_t)*wide >= A.n_wide) return 2;
@@ -142,17 +128,11 @@ MET_HD int met_family_check(const MetArgs &A, int64_t f, int32_t *wide) {
 // 1)][k], sum / max reduce over the sink's lanes.  `lane` of S::kLanes takes columns 4 lane .. 4
 // lane + 3 of every round.
 template <class S>
-MET_HD void met_record(const MetArgs &A, int64_t f, int e, int32_t wide, int lane, S &sink) {
+BSDC_HD void met_record(const MetArgs &A, int64_t f, int e, int32_t wide, int lane, S &sink) {
     const int L = (int)A.len[2 * f + e];
-    // strand rows (0, 3) for R1 and (1, 2) for R2; a = the AB row or the only one present
-    bool two = false;
-    int sa = e, sb = 3 - e;
-    if (A.kind == 0) {
-        const bool la = A.ss_len[4 * f + sa] > 0, lb = A.ss_len[4 * f + sb] > 0;
-        two = la && lb;
-        if (!la) sa = sb;
-    }
-    const MetRow a = met_row(A, f, sa, wide), b = met_row(A, f, sb, wide);
+    const bsdc_ssrows::End s = bsdc_ssrows::end_rows(A.kind, A.ss_len, f, e);
+    const bool two = s.two;
+    const Row a = bsdc_ssrows::row_of(A, f, s.a, wide), b = bsdc_ssrows::row_of(A, f, s.b, wide);
     const uint8_t *const seq = A.seq + (size_t)(2 * f + e) * (size_t)(A.stride >> 1);
     const uint8_t *const qual = A.qual + (size_t)(2 * f + e) * (size_t)A.stride;
 
@@ -184,8 +164,8 @@ MET_HD void met_record(const MetArgs &A, int64_t f, int e, int32_t wide, int lan
                 sbd += bd[j];
                 sbe += be[j];
                 mbd = mbd > bd[j] ? mbd : bd[j];
-                // the duplex call before its N mask; a strand whose call agrees with it contributes
-                // its errors, one that disagrees all of its reads
+                // bsdc_ssrows::duplex_col, written out: through the call k_metrics came out with 28
+                // more exec-mask branches and ran 4.5% slower (0.785 against 0.751 ms, 200k families)
                 const uint32_t x = ab[j] & 15u, y = bb[j] & 15u;
                 const uint32_t raw = x == y ? x : aq[j] > bq[j] ? x : bq[j] > aq[j] ? y : x;
                 const uint32_t td = ad[j] + bd[j];
@@ -217,8 +197,9 @@ MET_HD void met_record(const MetArgs &A, int64_t f, int e, int32_t wide, int lan
     }
     if (lane != 0) return;
     // the per-read values as the tag encoder writes them: float32 divides, NaN with no depth
-    const float aE = (float)sae / (float)sad, cE = (float)ste / (float)std_;
-    const float bE = two ? (float)sbe / (float)sbd : 0.0f;
+    using bsdc_ssrows::read_rate;
+    const float aE = read_rate(sae, sad), cE = read_rate(ste, std_);
+    const float bE = two ? read_rate(sbe, sbd) : 0.0f;
     const uint32_t D[3] = {mcd, mad, two ? mbd : 0u};
     const float E[3] = {cE, aE, bE};
     for (int k = 0; k < 3; k++) {
@@ -309,19 +290,8 @@ struct DevSink {
     uint32_t *hist32, *cyc32;
     unsigned long long *ovf;
     int32_t cycles, cyc4;
-    __device__ __forceinline__ uint32_t sum(uint32_t v) const {
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
-        return v;
-    }
-    __device__ __forceinline__ uint32_t max(uint32_t v) const {
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) {
-            const uint32_t o = (uint32_t)__shfl_xor((int)v, m, 64);
-            v = v > o ? v : o;
-        }
-        return v;
-    }
+    __device__ __forceinline__ uint32_t sum(uint32_t v) const { return bsdc_devtext::wave_sum(v); }
+    __device__ __forceinline__ uint32_t max(uint32_t v) const { return bsdc_devtext::wave_max(v); }
     __device__ __forceinline__ void hist(int w) { atomicAdd(&hist32[w], 1u); }
     __device__ __forceinline__ void cyc(int e, int c, int k, uint32_t v) {
         if (c < cycles - 1)
@@ -412,12 +382,8 @@ __global__ __launch_bounds__(256) void k_metrics_filter(const uint8_t *status, c
         for (int k = 0; k < 4; k++) v[1 + k] += (r >> k) & 1u;
         nm += (uint64_t)masked[2 * f] + masked[2 * f + 1];
     }
-    for (int k = 0; k < 5; k++) {
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) v[k] += (uint32_t)__shfl_xor((int)v[k], m, 64);
-    }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) nm += (uint64_t)__shfl_xor((long long)nm, m, 64);
+    for (int k = 0; k < 5; k++) v[k] = bsdc_devtext::wave_sum(v[k]);
+    nm = bsdc_devtext::wave_sum(nm);
     if ((threadIdx.x & 63) == 0) {
         for (int k = 0; k < 5; k++)
             if (v[k]) atomicAdd(&acc[BSDC_METRICS_KEPT + k], (unsigned long long)v[k]);

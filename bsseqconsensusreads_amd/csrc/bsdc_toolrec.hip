@@ -11,10 +11,10 @@
 //     over the wave; the record's size and its bin (htslib's reg2bin) land in `tmp`, 2 dwords a record;
 //  2-4. the offset scan of bsdc_devtext.h over the records' byte counts -> off[r];
 //  5. k_toolrec_write: one wavefront per record.  A record starts at any byte, so a lane owns one
-//     ALIGNED dword of the destination at a time, assembles its four bytes in a register and
-//     stores it whole; only a record's first and last partial dword (and a dword that would cross
-//     `cap`) leave as single bytes.  A dword inside QUAL, packed SEQ or the aux bytes is made of
-//     aligned source dwords by a funnel shift (tr_load4, tr_pack4); the fixed fields, the name,
+//     ALIGNED dword of the destination at a time (bsdc_devtext.h store_record), assembles its four
+//     bytes in a register and stores it whole; only a record's first and last partial dword (and a
+//     dword that would cross `cap`) leave as single bytes.  A dword inside QUAL, packed SEQ or the
+//     aux bytes is made of aligned source dwords by a funnel shift (load4, tr_pack4); the fixed fields, the name,
 //     the cigar, the RD / LA tags and the seams go byte by byte.
 // Bounds: a record whose table entry leaves the name / cigar / aux buffers has size 0 (the launcher
 // refuses such a table from the caller's host copy before anything runs); a record whose dump
@@ -30,17 +30,11 @@
 #include <string>
 
 #include "../../include/bsdc.h"
-
-#ifdef __HIPCC__
-#include <hip/hip_runtime.h>
-
 #include "bsdc_devtext.h"
-#define TR_HD __host__ __device__ __forceinline__
-#else
-#define TR_HD inline
-#endif
 
 namespace {
+
+using namespace bsdc_devtext;
 
 constexpr int kTrMaxName = 254;           // l_read_name <= 255 with its NUL
 constexpr int kTrMaxCig = 65533;          // + the prepended and the appended 1M: n_cigar_op <= 65535
@@ -67,30 +61,16 @@ struct TrArgs {
     int64_t groups;
 };
 
-TR_HD int64_t scan_bytes(const TrArgs &A, int64_t r, int) { return (int64_t)A.stat[r * kTrStat]; }
-TR_HD int64_t *scan_off(const TrArgs &A, int) { return A.off; }
+BSDC_HD int64_t scan_bytes(const TrArgs &A, int64_t r, int) { return (int64_t)A.stat[r * kTrStat]; }
+BSDC_HD int64_t *scan_off(const TrArgs &A, int) { return A.off; }
 
-// bytes a[0..3] as one little-endian dword by two aligned loads and a funnel shift; the aligned
-// dwords that hold a[0] and a[3] are read (the caller keeps both inside the buffer)
-TR_HD uint32_t tr_load4(const uint8_t *a) {
-    const int sh = (int)((uintptr_t)a & 3u);
-    uint32_t x, y;
-    memcpy(&x, __builtin_assume_aligned(a - sh, 4), 4);
-    if (!sh) return x;
-    memcpy(&y, __builtin_assume_aligned(a - sh + 4, 4), 4);
-    return (x >> (8 * sh)) | (y << (32 - 8 * sh));
-}
-// a[0..3] is inside [buf, buf + n) with the aligned dwords that hold a[0] and a[3] (buf 4-byte aligned)
-TR_HD bool tr_can4(const uint8_t *buf, int64_t n, const uint8_t *a) {
-    return a >= buf && (int64_t)((a + 3 - buf) | 3) < n;
-}
 // four nt16 codes, one per byte -> two packed bytes (high nibble first)
-TR_HD uint32_t tr_pack4(uint32_t x) {
+BSDC_HD uint32_t tr_pack4(uint32_t x) {
     return ((x & 0xfu) << 4) | ((x >> 8) & 0xfu) | ((x >> 12) & 0xf0u) << 8 | ((x >> 24) & 0xfu) << 8;
 }
 
 // htslib's reg2bin over [beg, end)
-TR_HD uint32_t tr_reg2bin(int64_t beg, int64_t end) {
+BSDC_HD uint32_t tr_reg2bin(int64_t beg, int64_t end) {
     --end;
     if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14)) & 0xffffu;
     if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17)) & 0xffffu;
@@ -111,7 +91,7 @@ struct TrRec {
     int o_cig, o_seq, o_qual, o_aux, o_tags, size;
 };
 
-TR_HD TrRec tr_rec(const TrArgs &A, int64_t r) {
+BSDC_HD TrRec tr_rec(const TrArgs &A, int64_t r) {
     TrRec q;
     const bsdc_toolrec_rec e = A.tab[r];
     q.ok = e.name_len >= 1 && e.name_len <= kTrMaxName && e.name_off >= 0 && e.name_off + e.name_len <= A.name_bytes &&
@@ -153,28 +133,28 @@ TR_HD TrRec tr_rec(const TrArgs &A, int64_t r) {
 }
 
 // op j of the record's new cigar (0 <= j < nc)
-TR_HD uint32_t tr_op(const TrRec &q, int j) {
+BSDC_HD uint32_t tr_op(const TrRec &q, int j) {
     if (j >= q.body || j < q.pre) return kOp1M;
     const uint32_t op = q.cg[j - q.pre];
     return q.dec && j == q.body - 1 ? op - kOp1M : op;
 }
 // the reference bases an op consumes: M D N = X
-TR_HD int64_t tr_op_ref(uint32_t op) {
+BSDC_HD int64_t tr_op_ref(uint32_t op) {
     const uint32_t k = op & 15u;
     return (k == 0 || k == 2 || k == 3 || k == 7 || k == 8) ? (int64_t)(op >> 4) : 0;
 }
 // this lane's share of the new cigar's reference length (lanes lane, lane + nl, ..)
-TR_HD int64_t tr_reflen_part(const TrRec &q, int lane, int nlanes) {
+BSDC_HD int64_t tr_reflen_part(const TrRec &q, int lane, int nlanes) {
     int64_t s = 0;
     for (int j = lane; j < q.nc; j += nlanes) s += tr_op_ref(tr_op(q, j));
     return s;
 }
-TR_HD uint32_t tr_bin(const TrRec &q, int64_t reflen) {
+BSDC_HD uint32_t tr_bin(const TrRec &q, int64_t reflen) {
     return tr_reg2bin((int64_t)q.pos, (int64_t)q.pos + (reflen > 0 ? reflen : 1));
 }
 
 // dword w of the record's first 36 bytes
-TR_HD uint32_t tr_fixed(const TrRec &q, uint32_t bin, int w) {
+BSDC_HD uint32_t tr_fixed(const TrRec &q, uint32_t bin, int w) {
     switch (w) {
     case 0: return (uint32_t)(q.size - 4);
     case 1: return (uint32_t)q.ref_id;
@@ -189,7 +169,7 @@ TR_HD uint32_t tr_fixed(const TrRec &q, uint32_t bin, int w) {
 }
 
 // byte i of the record (0 outside it)
-TR_HD uint32_t tr_byte(const TrRec &q, uint32_t bin, int i) {
+BSDC_HD uint32_t tr_byte(const TrRec &q, uint32_t bin, int i) {
     if (i < 0 || i >= q.size) return 0;
     if (i < 36) return (tr_fixed(q, bin, i >> 2) >> (8 * (i & 3))) & 0xffu;
     if (i < q.o_cig) return i - 36 < q.nl ? (uint32_t)q.nm[i - 36] : 0u;
@@ -205,17 +185,17 @@ TR_HD uint32_t tr_byte(const TrRec &q, uint32_t bin, int i) {
 }
 
 // bytes i0 .. i0 + 3 of the record as one little-endian dword (bytes outside the record: 0)
-TR_HD uint32_t tr_dword(const TrArgs &A, const TrRec &q, uint32_t bin, int i0) {
+BSDC_HD uint32_t tr_dword(const TrArgs &A, const TrRec &q, uint32_t bin, int i0) {
     if (i0 >= q.o_qual && i0 + 4 <= q.o_aux) {
         const uint8_t *a = q.ql + (i0 - q.o_qual);
-        if (tr_can4(A.dump_qual, A.n_dump, a)) return tr_load4(a);
+        if (can4(A.dump_qual, A.n_dump, a)) return load4(a);
     } else if (i0 >= q.o_seq && i0 + 4 <= q.o_seq + q.L / 2) {  // (whole bytes only: eight codes inside the read)
         const uint8_t *a = q.sq + 2 * (i0 - q.o_seq);
-        if (tr_can4(A.dump_seq, A.n_dump, a) && tr_can4(A.dump_seq, A.n_dump, a + 4))
-            return tr_pack4(tr_load4(a)) | tr_pack4(tr_load4(a + 4)) << 16;
+        if (can4(A.dump_seq, A.n_dump, a) && can4(A.dump_seq, A.n_dump, a + 4))
+            return tr_pack4(load4(a)) | tr_pack4(load4(a + 4)) << 16;
     } else if (i0 >= q.o_aux && i0 + 4 <= q.o_tags) {
         const uint8_t *a = q.ax + (i0 - q.o_aux);
-        if (tr_can4(A.aux, A.aux_bytes, a)) return tr_load4(a);
+        if (can4(A.aux, A.aux_bytes, a)) return load4(a);
     }
     uint32_t x = 0;
     for (int b = 0; b < 4; b++) x |= tr_byte(q, bin, i0 + b) << (8 * b);
@@ -223,22 +203,8 @@ TR_HD uint32_t tr_dword(const TrArgs &A, const TrRec &q, uint32_t bin, int i0) {
 }
 
 // the record's bytes at dst + o, this lane's dwords (lanes lane, lane + nlanes, ..)
-TR_HD void tr_store(const TrArgs &A, const TrRec &q, uint32_t bin, int64_t o, int lane, int nlanes) {
-    uint8_t *base = A.dst;
-    const int ho = (int)((uintptr_t)(base + o) & 3u);
-    const int nd = (ho + q.size + 3) >> 2;
-    for (int k = lane; k < nd; k += nlanes) {
-        // dword k covers the record's bytes 4k - ho ..; ho = the start's offset in its dword
-        const int i0 = 4 * k - ho;
-        const uint32_t v = tr_dword(A, q, bin, i0);
-        const int64_t p = o + i0;
-        if (i0 >= 0 && i0 + 4 <= q.size && p + 4 <= A.cap) {
-            memcpy(__builtin_assume_aligned(base + p, 4), &v, 4);  // (aligned: one dword store)
-            continue;
-        }
-        for (int b = 0; b < 4; b++)
-            if (i0 + b >= 0 && i0 + b < q.size && p + b < A.cap) base[p + b] = (uint8_t)(v >> (8 * b));
-    }
+BSDC_HD void tr_store(const TrArgs &A, const TrRec &q, uint32_t bin, int64_t o, int lane, int nlanes) {
+    store_record(A.dst, o, q.size, A.cap, lane, nlanes, [&](int i0) { return tr_dword(A, q, bin, i0); });
 }
 
 thread_local std::string g_tr_err;
@@ -308,22 +274,12 @@ int32_t tr_check(const char *who, const bsdc_consensus *out, const uint32_t *rec
 }
 
 #ifdef __HIPCC__
-using namespace bsdc_devtext;
-
-__device__ __forceinline__ int64_t tr_wave_sum(int64_t v) {
-    for (int o = 32; o; o >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)((uint64_t)v >> 32), o);
-        v += (int64_t)((uint64_t)hi << 32 | lo);
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(kT) void k_toolrec_sizes(TrArgs A) {
     const int64_t r = (int64_t)blockIdx.x * (kT / 64) + (threadIdx.x >> 6);
     if (r >= A.n_fam) return;
     const int lane = threadIdx.x & 63;
     const TrRec q = tr_rec(A, r);
-    const int64_t reflen = tr_wave_sum(tr_reflen_part(q, lane, 64));
+    const int64_t reflen = wave_sum(tr_reflen_part(q, lane, 64));
     if (lane < kTrStat) A.stat[r * kTrStat + lane] = lane == 0 ? (uint32_t)q.size : tr_bin(q, reflen);
 }
 

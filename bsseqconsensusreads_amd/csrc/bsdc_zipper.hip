@@ -16,7 +16,8 @@
 // bsdc_zip_format: one wavefront per output record, in sorted order: k_zip_sizes, the offset scan,
 // k_zip_write.  Every lane walks the two aux lists by type (the same walk in all lanes) to decide
 // which tags stay and which are flipped; runs of tags that are copied as they are leave by
-// "a lane owns one aligned destination dword" (funnel-shifted source dwords), a flipped Z or B
+// "a lane owns one aligned destination dword" (funnel-shifted source dwords: bsdc_devtext.h load4 /
+// can4; zp_copy keeps its own loop, which picks dword or bytes by the source too), a flipped Z or B
 // payload by the lane that owns the destination byte / element.
 // Bounds: a table entry that leaves the byte buffers makes a record of size 0 (the launcher
 // refuses it from the host copy first); a sorted index >= n likewise; a walk stops at a tag that
@@ -30,17 +31,11 @@
 #include <vector>
 
 #include "../../include/bsdc.h"
-
-#ifdef __HIPCC__
-#include <hip/hip_runtime.h>
-
 #include "bsdc_devtext.h"
-#define ZP_HD __host__ __device__ __forceinline__
-#else
-#define ZP_HD inline
-#endif
 
 namespace {
+
+using namespace bsdc_devtext;
 
 constexpr int kZsBits = 8;                 // bits a pass
 constexpr int kZsBins = 1 << kZsBits;
@@ -53,14 +48,14 @@ constexpr int kZipStat = 1;                // dwords per record in tmp: size
 
 // ---- the sort ----
 
-ZP_HD uint32_t zs_digit(uint64_t key, int pass) { return (uint32_t)(key >> (kZsBits * pass)) & (kZsBins - 1); }
+BSDC_HD uint32_t zs_digit(uint64_t key, int pass) { return (uint32_t)(key >> (kZsBits * pass)) & (kZsBins - 1); }
 
 // the largest key of refID <= max_ref, pos <= max_pos
-ZP_HD uint64_t zs_max_key(int32_t max_ref, int32_t max_pos) {
+BSDC_HD uint64_t zs_max_key(int32_t max_ref, int32_t max_pos) {
     return (uint64_t)(uint32_t)max_ref << 32 | (uint64_t)((uint32_t)(max_pos + 1)) << 1 | 1u;
 }
 // a pass whose digit is zero in every key is skipped: the two halves of the key are bounded apart
-ZP_HD bool zs_pass_needed(int32_t max_ref, int32_t max_pos, int pass) {
+BSDC_HD bool zs_pass_needed(int32_t max_ref, int32_t max_pos, int pass) {
     const uint64_t m = zs_max_key(max_ref, max_pos);
     const uint32_t half = pass < 4 ? (uint32_t)m : (uint32_t)(m >> 32);
     return (half >> (kZsBits * (pass & 3))) != 0;
@@ -83,24 +78,11 @@ struct ZpArgs {
     int64_t groups;
 };
 
-ZP_HD int64_t scan_bytes(const ZpArgs &A, int64_t r, int) { return (int64_t)A.stat[r * kZipStat]; }
-ZP_HD int64_t *scan_off(const ZpArgs &A, int) { return A.off; }
-
-ZP_HD uint32_t zp_load4(const uint8_t *a) {
-    const int sh = (int)((uintptr_t)a & 3u);
-    uint32_t x, y;
-    memcpy(&x, __builtin_assume_aligned(a - sh, 4), 4);
-    if (!sh) return x;
-    memcpy(&y, __builtin_assume_aligned(a - sh + 4, 4), 4);
-    return (x >> (8 * sh)) | (y << (32 - 8 * sh));
-}
-// a[0..3] is inside [buf, buf + n) with the aligned dwords that hold a[0] and a[3] (buf 4-byte aligned)
-ZP_HD bool zp_can4(const uint8_t *buf, int64_t n, const uint8_t *a) {
-    return a >= buf && (int64_t)((a + 3 - buf) | 3) < n;
-}
+BSDC_HD int64_t scan_bytes(const ZpArgs &A, int64_t r, int) { return (int64_t)A.stat[r * kZipStat]; }
+BSDC_HD int64_t *scan_off(const ZpArgs &A, int) { return A.off; }
 
 // the value bytes of a fixed-size aux type, 0 for any other
-ZP_HD int zp_fixed(uint8_t t) {
+BSDC_HD int zp_fixed(uint8_t t) {
     switch (t) {
     case 'A': case 'c': case 'C': return 1;
     case 's': case 'S': return 2;
@@ -109,7 +91,7 @@ ZP_HD int zp_fixed(uint8_t t) {
     }
 }
 // the end of the tag at a[i] in an aux block of n bytes; -1: an unknown type or a tag that leaves the block
-ZP_HD int64_t zp_tag_end(const uint8_t *a, int64_t i, int64_t n) {
+BSDC_HD int64_t zp_tag_end(const uint8_t *a, int64_t i, int64_t n) {
     if (i + 3 > n) return -1;
     const uint8_t t = a[i + 2];
     int64_t j;
@@ -131,13 +113,13 @@ ZP_HD int64_t zp_tag_end(const uint8_t *a, int64_t i, int64_t n) {
     }
     return j <= n ? j : -1;
 }
-ZP_HD bool zp_listed(const uint8_t *names, int n, uint8_t c0, uint8_t c1) {
+BSDC_HD bool zp_listed(const uint8_t *names, int n, uint8_t c0, uint8_t c1) {
     for (int k = 0; k < n; k++)
         if (names[2 * k] == c0 && names[2 * k + 1] == c1) return true;
     return false;
 }
 // a tag of this name occurs in the aux block (walked by type)
-ZP_HD bool zp_in_aux(const uint8_t *a, int64_t n, uint8_t c0, uint8_t c1) {
+BSDC_HD bool zp_in_aux(const uint8_t *a, int64_t n, uint8_t c0, uint8_t c1) {
     for (int64_t i = 0; i < n;) {
         const int64_t j = zp_tag_end(a, i, n);
         if (j < 0) break;
@@ -146,7 +128,7 @@ ZP_HD bool zp_in_aux(const uint8_t *a, int64_t n, uint8_t c0, uint8_t c1) {
     }
     return false;
 }
-ZP_HD uint8_t zp_comp(uint8_t c) {
+BSDC_HD uint8_t zp_comp(uint8_t c) {
     switch (c) {
     case 'A': return 'T'; case 'T': return 'A'; case 'C': return 'G'; case 'G': return 'C';
     case 'a': return 't'; case 't': return 'a'; case 'c': return 'g'; case 'g': return 'c';
@@ -161,7 +143,7 @@ struct ZpRec {
     uint32_t flag;
 };
 
-ZP_HD ZpRec zp_rec(const ZpArgs &A, int64_t k) {
+BSDC_HD ZpRec zp_rec(const ZpArgs &A, int64_t k) {
     ZpRec q;
     const uint32_t s = A.idx[k];
     bsdc_zip_rec e;
@@ -180,7 +162,7 @@ ZP_HD ZpRec zp_rec(const ZpArgs &A, int64_t k) {
 }
 
 // byte i of the record's part before the aux: block_size and the flag are the output's
-ZP_HD uint8_t zp_head_byte(const ZpRec &q, uint32_t size, int64_t i) {
+BSDC_HD uint8_t zp_head_byte(const ZpRec &q, uint32_t size, int64_t i) {
     if (i < 4) return (uint8_t)((size - 4) >> (8 * i));
     if (i == 18) return (uint8_t)q.flag;
     if (i == 19) return (uint8_t)(q.flag >> 8);
@@ -189,7 +171,7 @@ ZP_HD uint8_t zp_head_byte(const ZpRec &q, uint32_t size, int64_t i) {
 
 // src[0 .. len) to dst + o, this lane's dwords; HEAD: the bytes are the record's first ones (zp_head_byte)
 template <bool HEAD>
-ZP_HD void zp_copy(const ZpArgs &A, const ZpRec &q, uint32_t size, const uint8_t *buf, int64_t buf_n, const uint8_t *src,
+BSDC_HD void zp_copy(const ZpArgs &A, const ZpRec &q, uint32_t size, const uint8_t *buf, int64_t buf_n, const uint8_t *src,
                    int64_t len, int64_t o, int lane, int nlanes) {
     uint8_t *base = A.dst;
     const int ho = (int)((uintptr_t)(base + o) & 3u);
@@ -197,8 +179,8 @@ ZP_HD void zp_copy(const ZpArgs &A, const ZpRec &q, uint32_t size, const uint8_t
     for (int64_t k = lane; k < nd; k += nlanes) {
         const int64_t i0 = 4 * k - ho, p = o + i0;
         const bool patched = HEAD && (i0 < 4 || (i0 < 20 && i0 + 4 > 16));
-        if (i0 >= 0 && i0 + 4 <= len && p + 4 <= A.cap && !patched && zp_can4(buf, buf_n, src + i0)) {
-            const uint32_t v = zp_load4(src + i0);
+        if (i0 >= 0 && i0 + 4 <= len && p + 4 <= A.cap && !patched && can4(buf, buf_n, src + i0)) {
+            const uint32_t v = load4(src + i0);
             memcpy(__builtin_assume_aligned(base + p, 4), &v, 4);  // (aligned: one dword store)
             continue;
         }
@@ -210,7 +192,7 @@ ZP_HD void zp_copy(const ZpArgs &A, const ZpRec &q, uint32_t size, const uint8_t
 }
 
 // what rule 5 does to a partner's tag of an output record with flag 0x10: 0 nothing, 1 reversed, 2 reverse-complemented
-ZP_HD int zp_mode(const ZpArgs &A, const uint8_t *t) {
+BSDC_HD int zp_mode(const ZpArgs &A, const uint8_t *t) {
     const bool rv = zp_listed(A.tags.reverse, A.tags.n_reverse, t[0], t[1]);
     if (t[2] == 'B') return rv ? 1 : 0;
     if (t[2] != 'Z') return 0;
@@ -218,7 +200,7 @@ ZP_HD int zp_mode(const ZpArgs &A, const uint8_t *t) {
 }
 
 // the tag t[0 .. len) flipped to dst + o: a lane writes the destination bytes (Z) or elements (B) it owns
-ZP_HD void zp_flip(const ZpArgs &A, const uint8_t *t, int64_t len, int mode, int64_t o, int lane, int nlanes) {
+BSDC_HD void zp_flip(const ZpArgs &A, const uint8_t *t, int64_t len, int mode, int64_t o, int lane, int nlanes) {
     uint8_t *base = A.dst;
     if (t[2] == 'Z') {
         const int64_t m = len - 4;  // the string without its NUL
@@ -245,7 +227,7 @@ ZP_HD void zp_flip(const ZpArgs &A, const uint8_t *t, int64_t len, int mode, int
 
 // The record at dst + o (WRITE) -> its size.  `size`: what the size pass gave (the block_size field).
 template <bool WRITE>
-ZP_HD int64_t zp_emit(const ZpArgs &A, const ZpRec &q, uint32_t size, int64_t o, int lane, int nlanes) {
+BSDC_HD int64_t zp_emit(const ZpArgs &A, const ZpRec &q, uint32_t size, int64_t o, int lane, int nlanes) {
     if (q.rn == 0) return 0;
     int64_t w = q.ra;
     if (WRITE) zp_copy<true>(A, q, size, A.rec, A.rec_bytes, q.r, q.ra, o, lane, nlanes);
@@ -392,8 +374,6 @@ int32_t zs_check(const char *who, const uint64_t *keys, const uint32_t *idx, int
 }
 
 #ifdef __HIPCC__
-using namespace bsdc_devtext;
-
 struct ZsArgs {
     const uint64_t *kin;
     const uint32_t *vin;
@@ -407,8 +387,8 @@ struct ZsArgs {
     int64_t *bsum;
     int64_t groups;
 };
-__host__ __device__ __forceinline__ int64_t scan_bytes(const ZsArgs &A, int64_t i, int) { return (int64_t)A.hist[i]; }
-__host__ __device__ __forceinline__ int64_t *scan_off(const ZsArgs &A, int) { return A.off; }
+BSDC_HD int64_t scan_bytes(const ZsArgs &A, int64_t i, int) { return (int64_t)A.hist[i]; }
+BSDC_HD int64_t *scan_off(const ZsArgs &A, int) { return A.off; }
 
 __global__ __launch_bounds__(kZsThreads) void k_zs_hist(ZsArgs A) {
     __shared__ uint32_t h[kZsBins];
