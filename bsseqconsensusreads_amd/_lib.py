@@ -51,6 +51,8 @@ ZIP_REC = [("rec_off", "<i8"), ("part_off", "<i8"), ("rec_len", "<i4"), ("aux_st
 ZIP_SRC = [("off", "<i8"), ("len", "<i4"), ("aux", "<i4"), ("ref_id", "<i4"), ("pos", "<i4"), ("flag", "<u2"),
            ("name_len", "u1"), ("reserved0", "u1"), ("reserved", "<i4")]
 ZIP_MAX_TAGS = 32  # BSDC_ZIP_MAX_TAGS
+# bsdc_group_rec as a numpy record: cli group's record table (group.py)
+GROUP_REC = [("off", "<i8"), ("len", "<i4"), ("aux", "<i4")]
 
 
 class ZipTagsC(C.Structure):  # bsdc_zip_tags
@@ -97,7 +99,9 @@ EXPORTS = ("bsdc_abi_version", "bsdc_ctx_create", "bsdc_ctx_set_params", "bsdc_c
            "bsdc_toolrec_bytes_bound", "bsdc_toolrec_tmp_bytes", "bsdc_toolrec_format", "bsdc_toolrec_host",
            "bsdc_toolrec_last_error", "bsdc_zip_sort_tile", "bsdc_zip_sort_tmp_bytes", "bsdc_zip_sort",
            "bsdc_zip_sort_host", "bsdc_zip_bytes_bound", "bsdc_zip_format_tmp_bytes", "bsdc_zip_format",
-           "bsdc_zip_format_host", "bsdc_zip_scan_host", "bsdc_zip_last_error")
+           "bsdc_zip_format_host", "bsdc_zip_scan_host", "bsdc_zip_last_error", "bsdc_group_lds_nodes",
+           "bsdc_group_tmp_bytes", "bsdc_group_assign", "bsdc_group_assign_host", "bsdc_group_bytes_bound",
+           "bsdc_group_format_tmp_bytes", "bsdc_group_format", "bsdc_group_format_host", "bsdc_group_last_error")
 
 _lib = None
 
@@ -231,6 +235,27 @@ def load(path: str = LIB_PATH):
     lib.bsdc_zip_scan_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
     lib.bsdc_zip_scan_host.restype = C.c_int64
     lib.bsdc_zip_last_error.restype = C.c_char_p
+    lib.bsdc_group_lds_nodes.restype = C.c_int32
+    lib.bsdc_group_tmp_bytes.argtypes = [C.c_int64]
+    lib.bsdc_group_tmp_bytes.restype = C.c_int64
+    lib.bsdc_group_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bsdc_group_assign.restype = C.c_int32
+    lib.bsdc_group_assign_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bsdc_group_assign_host.restype = C.c_int32
+    lib.bsdc_group_bytes_bound.argtypes = [C.c_void_p, C.c_int64]
+    lib.bsdc_group_bytes_bound.restype = C.c_int64
+    lib.bsdc_group_format_tmp_bytes.argtypes = [C.c_int64]
+    lib.bsdc_group_format_tmp_bytes.restype = C.c_int64
+    lib.bsdc_group_format.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_int64, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                      C.c_void_p]
+    lib.bsdc_group_format.restype = C.c_int32
+    lib.bsdc_group_format_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                           C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.bsdc_group_format_host.restype = C.c_int32
+    lib.bsdc_group_last_error.restype = C.c_char_p
     if lib.bsdc_abi_version() != BSDC_ABI_VERSION:
         raise RuntimeError("libbsdc ABI %d != %d" % (lib.bsdc_abi_version(), BSDC_ABI_VERSION))
     if path == LIB_PATH:

@@ -1152,10 +1152,10 @@ def molecular(in_bam: str, out_bam: Optional[str], engine=None, prefix: Optional
 
 def __getattr__(name):
     """The streaming steps live in stream.py, the GPU BGZF codecs and the streaming writers in
-    bgzf.py, cli zipper's driver in zipper.py (all import this module); they stay importable from here."""
+    bgzf.py, cli zipper's driver in zipper.py, cli group's in group.py (all import this module); they stay importable from here."""
     home = {"step5_stream": "stream", "molecular_stream": "stream", "GpuBgzf": "bgzf", "GpuInflate": "bgzf",
             "_BgzfWriter": "bgzf", "BamWriter": "bgzf", "FastqWriter": "bgzf", "close_quietly": "bgzf",
-            "zipper": "zipper"}.get(name)
+            "zipper": "zipper", "group": "group"}.get(name)
     if home is None:
         raise AttributeError("module %r has no attribute %r" % (__name__, name))
     import importlib

@@ -15,6 +15,7 @@ step5 --groupsort-bam PATH also writes the records after tool 1 and tool 2 in Te
 order: the file rule groupsort_convert leaves (main.snake.py:144-153), the input of fgbio
 CallDuplexConsensusReads at :163 (--gpus 1 only).
 
+    python -m bsseqconsensusreads_amd.cli group IN.bam OUT.bam [--edits E] [--min-map-q Q] [--info PATH]
     python -m bsseqconsensusreads_amd.cli zipper ALIGNED.bam UNMAPPED.bam OUT.bam [--tags-to-reverse T..]
             [--tags-to-revcomp T..] [--tags-to-remove T..] [--info PATH]
         rules mergeAunA_consensus and mergeAunA_consensus_grepaligned (main.snake.py:97-119): the aligner's
@@ -138,7 +139,26 @@ def parse(argv):
     z.add_argument("--level", type=int, default=6, help="the output's deflate level")
     z.add_argument("--device", type=int, default=0)
     z.add_argument("--info", default=None, metavar="PATH", help="write the run's counts as one JSON file")
+    g = sub.add_parser("group")
+    g.add_argument("input", help="the aligned, UMI-tagged BAM (any order; read whole)")
+    g.add_argument("output", help="the grouped BAM (cli molecular's input)")
+    g.add_argument("--strategy", default="paired", help="only 'paired' is built")
+    g.add_argument("--edits", type=int, default=1, help="the most differing UMI bases that still join (0..3)")
+    g.add_argument("--min-map-q", type=int, default=1)
+    g.add_argument("--include-non-pf-reads", default="false", choices=("true", "false"))
+    g.add_argument("--raw-tag", default="RX")
+    g.add_argument("--assign-tag", default="MI")
+    g.add_argument("--threads", type=int, default=8)
+    g.add_argument("--level", type=int, default=6, help="the output's deflate level")
+    g.add_argument("--device", type=int, default=0)
+    g.add_argument("--info", default=None, metavar="PATH", help="write the run's counts as one JSON file")
     a = ap.parse_args(argv)
+    if a.cmd == "group":
+        if a.strategy.lower() != "paired":
+            ap.error("--strategy %s is not built: only 'paired' is" % a.strategy)
+        if not 0 <= a.edits <= 3:
+            ap.error("--edits takes 0..3")
+        return a
     if a.cmd == "zipper":
         return a
     others = [k for k in ("min_reads", "max_read_error_rate", "max_base_error_rate", "max_no_call_fraction",
@@ -263,9 +283,24 @@ def _zipper(a) -> int:
     return 0
 
 
+def _group(a) -> int:
+    """cli group: fgbio GroupReadsByUmi -s Paired on one GPU (group.group)."""
+    try:
+        from . import bam
+        info = bam.group(a.input, a.output, a.edits, a.min_map_q, a.include_non_pf_reads == "true", a.raw_tag,
+                         a.assign_tag, a.strategy, threads=a.threads, level=a.level, device=a.device, info=a.info)
+    except Exception as e:  # noqa: BLE001 -- the rule fails with the message
+        print("%s: %s" % (type(e).__name__, e), file=sys.stderr)
+        return 1
+    print(json.dumps(info), file=sys.stderr)
+    return 0
+
+
 def main(argv=None) -> int:
     argv = sys.argv[1:] if argv is None else list(argv)
     a = parse(argv)
+    if a.cmd == "group":
+        return _group(a)
     if a.cmd == "zipper":
         return _zipper(a)
     from . import bam, shard

@@ -611,6 +611,64 @@ int32_t bsdc_zip_format_host(const uint32_t *idx, int64_t n, const bsdc_zip_rec 
 int64_t bsdc_zip_scan_host(const uint8_t *bytes, int64_t n_bytes, bsdc_zip_src *out, int64_t cap);
 const char *bsdc_zip_last_error(void);
 
+/* (new exports, ABI 19 still) cli group: paired-UMI molecule ids for the templates of a tagged BAM
+ * -- fgbio GroupReadsByUmi -s Paired restated, parity unpinned (the input of rule
+ * CallMolecularConsensusReads; csrc/bsdc_group.hip, DESIGN.md sections 3.12 and 8.13).
+ *
+ * bsdc_group_assign: n templates in read-name order.  k0 / k1 [n]: the packed position key of the
+ * lower / higher end (refID << 32 | biased 5' position << 1 | reverse: any encoding whose integer
+ * order is rule 2's); umi [n]: the canonical UMI, two bits a base, first half << 32 | second half;
+ * strand [n]: 0 top, 1 bottom; kmax [3] (host): a bound of k0, k1 and umi each (their maximum, or
+ * the OR of all values), by which sort passes over zero digits are skipped.  Position groups are
+ * the runs of equal (k0, k1) in ascending order; inside one, the templates of one umi form a node,
+ * the nodes are ordered by count descending, then umi ascending; walking them in that order an
+ * unassigned node becomes a root and enters a FIFO, and for each node p taken from the FIFO every
+ * still-unassigned node c with count(c) <= count(p) / 2 + 1 and hamming(umi(p), umi(c)) <= edits
+ * (0..3; differing bases over both halves) joins the root's molecule and enters the FIFO, in node
+ * order.  Molecule ids count from 0 over the groups in order, roots in their order.  Outputs:
+ * mol [n] the template's id; ab [n] 0 (/A) when its strand is that of the root node's first
+ * template (the lowest in name order), else 1 (/B); order [n] the templates by (id, ab, name
+ * order); stats [4] (host): position groups, nodes, molecules, the most nodes of a group.
+ * arena 0: a group of more than 64 nodes is walked in LDS when it has at most
+ * bsdc_group_lds_nodes() nodes, 1: always in the scratch.  tmp: bsdc_group_tmp_bytes(n), 8-byte
+ * aligned.  All but kmax and stats are device pointers; the call synchronises `stream` (it reads
+ * three counts back) and returns with everything done but the last sort, which is enqueued.
+ * bsdc_group_assign_host: the same on host pointers, group by group with the same join function.
+ *
+ * bsdc_group_format: output record 2k / 2k + 1 is R1 / R2 of template order[k] (tab [2n]: template
+ * t's records at 2t, 2t + 1): the input record's bytes with every tag named `tag` (two letters,
+ * NUL-terminated; the aux walked by type) left out, <tag>:Z:<mol>/<A|B> appended and block_size
+ * adjusted.  off [2n + 1] receives the records' offsets, off[2n] their bytes; no byte at or past
+ * dst + cap is written (bsdc_group_bytes_bound of the host table is a cap that holds).  BSDC_EINVAL
+ * before anything is enqueued, with the reason in bsdc_group_last_error (thread-local): a null
+ * pointer, a table entry that leaves rec, a malformed aux block (the read is named), a cap below
+ * the bound.  `order` is a device array the launcher does not read: an entry >= n makes a record of
+ * size 0 there (bsdc_group_format_host refuses it).  tmp: bsdc_group_format_tmp_bytes(n).
+ * bsdc_group_format_host: host pointers, the same per-record function run sequentially.
+ * Limits: bsdc_group_assign n <= 2^30 templates (bsdc_zip_sort's), bsdc_group_format n <= 2^29
+ * (2n records). */
+typedef struct bsdc_group_rec {
+    int64_t off; /* the record (its block_size field) in rec */
+    int32_t len; /* its bytes, block_size field included */
+    int32_t aux; /* where its aux block starts */
+} bsdc_group_rec;
+
+int32_t bsdc_group_lds_nodes(void);
+int64_t bsdc_group_tmp_bytes(int64_t n);
+int32_t bsdc_group_assign(const uint64_t *k0, const uint64_t *k1, const uint64_t *umi, const uint8_t *strand, int64_t n,
+                          int32_t edits, const uint64_t *kmax, int32_t arena, uint32_t *mol, uint8_t *ab, uint32_t *order,
+                          int64_t *stats, uint8_t *tmp, void *stream);
+int32_t bsdc_group_assign_host(const uint64_t *k0, const uint64_t *k1, const uint64_t *umi, const uint8_t *strand, int64_t n,
+                               int32_t edits, const uint64_t *kmax, uint32_t *mol, uint8_t *ab, uint32_t *order, int64_t *stats);
+int64_t bsdc_group_bytes_bound(const bsdc_group_rec *tab_host, int64_t n_rec);
+int64_t bsdc_group_format_tmp_bytes(int64_t n);
+int32_t bsdc_group_format(const uint32_t *order, const uint32_t *mol, const uint8_t *ab, int64_t n, const bsdc_group_rec *tab,
+                          const bsdc_group_rec *tab_host, const uint8_t *rec, const uint8_t *rec_host, int64_t rec_bytes,
+                          const char *tag, int64_t *off, uint8_t *dst, int64_t cap, uint8_t *tmp, void *stream);
+int32_t bsdc_group_format_host(const uint32_t *order, const uint32_t *mol, const uint8_t *ab, int64_t n, const bsdc_group_rec *tab,
+                               const uint8_t *rec, int64_t rec_bytes, const char *tag, int64_t *off, uint8_t *dst, int64_t cap);
+const char *bsdc_group_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif
