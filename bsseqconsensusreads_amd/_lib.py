@@ -99,7 +99,8 @@ EXPORTS = ("bsdc_abi_version", "bsdc_ctx_create", "bsdc_ctx_set_params", "bsdc_c
            "bsdc_toolrec_bytes_bound", "bsdc_toolrec_tmp_bytes", "bsdc_toolrec_format", "bsdc_toolrec_host",
            "bsdc_toolrec_last_error", "bsdc_zip_sort_tile", "bsdc_zip_sort_tmp_bytes", "bsdc_zip_sort",
            "bsdc_zip_sort_host", "bsdc_zip_bytes_bound", "bsdc_zip_format_tmp_bytes", "bsdc_zip_format",
-           "bsdc_zip_format_host", "bsdc_zip_scan_host", "bsdc_zip_last_error", "bsdc_group_lds_nodes",
+           "bsdc_zip_format_host", "bsdc_zip_scan_host", "bsdc_zip_scan_prefix_host", "bsdc_zip_gather_tmp_bytes",
+           "bsdc_zip_gather", "bsdc_zip_gather_host", "bsdc_zip_last_error", "bsdc_group_lds_nodes",
            "bsdc_group_tmp_bytes", "bsdc_group_assign", "bsdc_group_assign_host", "bsdc_group_bytes_bound",
            "bsdc_group_format_tmp_bytes", "bsdc_group_format", "bsdc_group_format_host", "bsdc_group_last_error")
 
@@ -234,6 +235,16 @@ def load(path: str = LIB_PATH):
     lib.bsdc_zip_format_host.restype = C.c_int32
     lib.bsdc_zip_scan_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
     lib.bsdc_zip_scan_host.restype = C.c_int64
+    lib.bsdc_zip_scan_prefix_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    lib.bsdc_zip_scan_prefix_host.restype = C.c_int64
+    lib.bsdc_zip_gather_tmp_bytes.argtypes = [C.c_int64]
+    lib.bsdc_zip_gather_tmp_bytes.restype = C.c_int64
+    lib.bsdc_zip_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.bsdc_zip_gather.restype = C.c_int32
+    lib.bsdc_zip_gather_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.c_void_p, C.c_int64]
+    lib.bsdc_zip_gather_host.restype = C.c_int32
     lib.bsdc_zip_last_error.restype = C.c_char_p
     lib.bsdc_group_lds_nodes.restype = C.c_int32
     lib.bsdc_group_tmp_bytes.argtypes = [C.c_int64]

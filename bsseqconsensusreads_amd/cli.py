@@ -17,10 +17,12 @@ CallDuplexConsensusReads at :163 (--gpus 1 only).
 
     python -m bsseqconsensusreads_amd.cli group IN.bam OUT.bam [--edits E] [--min-map-q Q] [--info PATH]
     python -m bsseqconsensusreads_amd.cli zipper ALIGNED.bam UNMAPPED.bam OUT.bam [--tags-to-reverse T..]
-            [--tags-to-revcomp T..] [--tags-to-remove T..] [--info PATH]
+            [--tags-to-revcomp T..] [--tags-to-remove T..] [--info PATH] [--stream true --chunk-mb M --tmp-dir DIR]
         rules mergeAunA_consensus and mergeAunA_consensus_grepaligned (main.snake.py:97-119): the aligner's
         records with MI, RX, RG and the consensus tags put back from the step-1 BAM, unmapped records
-        dropped, coordinate-sorted on the GPU (both inputs are read whole)
+        dropped, coordinate-sorted on the GPU.  --stream true: memory bounded by
+        --chunk-mb (default 1024) -- sorted runs under --tmp-dir, merged on the GPU; ALIGNED must keep
+        UNMAPPED's template order, as bwa mem leaves it.  --stream false (the default) reads both inputs whole.
 
 OUT.bam may be '-' to skip the BAM when only the FASTQ pair is wanted.  Errors exit non-zero with
 the message on stderr, so Snakemake aborts the rule and removes partial outputs, as it does for
@@ -139,6 +141,12 @@ def parse(argv):
     z.add_argument("--level", type=int, default=6, help="the output's deflate level")
     z.add_argument("--device", type=int, default=0)
     z.add_argument("--info", default=None, metavar="PATH", help="write the run's counts as one JSON file")
+    z.add_argument("--stream", default="false", choices=("true", "false"),
+                   help="bounded memory: sorted runs of --chunk-mb each, merged on the GPU; needs ALIGNED to keep "
+                        "UNMAPPED's template order, as bwa mem leaves it (default false: both inputs are read whole)")
+    z.add_argument("--chunk-mb", type=int, default=1024, metavar="M",
+                   help="--stream true: the MiB of record bytes (ALIGNED's records and their partners' tags) a run holds")
+    z.add_argument("--tmp-dir", default=None, metavar="DIR", help="--stream true: where the runs are kept (default: OUT's directory)")
     g = sub.add_parser("group")
     g.add_argument("input", help="the aligned, UMI-tagged BAM (any order; read whole)")
     g.add_argument("output", help="the grouped BAM (cli molecular's input)")
@@ -160,6 +168,8 @@ def parse(argv):
             ap.error("--edits takes 0..3")
         return a
     if a.cmd == "zipper":
+        if a.chunk_mb < 1:
+            ap.error("--chunk-mb takes a positive number")
         return a
     others = [k for k in ("min_reads", "max_read_error_rate", "max_base_error_rate", "max_no_call_fraction",
                           "min_mean_base_quality", "require_single_strand_agreement")
@@ -275,7 +285,8 @@ def _zipper(a) -> int:
     try:
         from . import bam
         info = bam.zipper(a.aligned, a.unmapped, a.output, a.tags_to_reverse, a.tags_to_revcomp, a.tags_to_remove,
-                          threads=a.threads, level=a.level, device=a.device, info=a.info)
+                          threads=a.threads, level=a.level, device=a.device, info=a.info, stream=a.stream == "true",
+                          chunk_bytes=a.chunk_mb << 20, tmp_dir=a.tmp_dir)
     except Exception as e:  # noqa: BLE001 -- the rule fails with the message
         print("%s: %s" % (type(e).__name__, e), file=sys.stderr)
         return 1

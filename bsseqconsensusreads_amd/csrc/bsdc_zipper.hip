@@ -23,6 +23,11 @@
 // refuses it from the host copy first); a sorted index >= n likewise; a walk stops at a tag that
 // is unknown or leaves its aux block (the launcher refuses such records from the host copies, by
 // name); no byte at or past `cap` is written.
+//
+// bsdc_zip_gather (cli zipper --stream true's merge rounds): output record k is source record
+// order[k], unchanged: the offset scan over the table's lengths, then k_zip_gather, one wavefront
+// per record with k_zip_write's copy (zp_copy_to).  An order entry >= n or a table entry that
+// leaves src is a record of no bytes; the launcher refuses both from the host copies first.
 // Built without hipcc this file holds the twins alone.
 #include <stdint.h>
 #include <string.h>
@@ -139,25 +144,30 @@ BSDC_HD uint8_t zp_head_byte(const ZpRec &q, uint32_t size, int64_t i) {
 }
 
 // src[0 .. len) to dst + o, this lane's dwords; HEAD: the bytes are the record's first ones (zp_head_byte)
+// (zp_copy_to: the same on any destination of `cap` writable bytes -- bsdc_zip_gather's copy too)
 template <bool HEAD>
-BSDC_HD void zp_copy(const ZpArgs &A, const ZpRec &q, uint32_t size, const uint8_t *buf, int64_t buf_n, const uint8_t *src,
-                   int64_t len, int64_t o, int lane, int nlanes) {
-    uint8_t *base = A.dst;
+BSDC_HD void zp_copy_to(uint8_t *base, int64_t cap, const ZpRec &q, uint32_t size, const uint8_t *buf, int64_t buf_n,
+                      const uint8_t *src, int64_t len, int64_t o, int lane, int nlanes) {
     const int ho = (int)((uintptr_t)(base + o) & 3u);
     const int64_t nd = (ho + len + 3) >> 2;
     for (int64_t k = lane; k < nd; k += nlanes) {
         const int64_t i0 = 4 * k - ho, p = o + i0;
         const bool patched = HEAD && (i0 < 4 || (i0 < 20 && i0 + 4 > 16));
-        if (i0 >= 0 && i0 + 4 <= len && p + 4 <= A.cap && !patched && can4(buf, buf_n, src + i0)) {
+        if (i0 >= 0 && i0 + 4 <= len && p + 4 <= cap && !patched && can4(buf, buf_n, src + i0)) {
             const uint32_t v = load4(src + i0);
             memcpy(__builtin_assume_aligned(base + p, 4), &v, 4);  // (aligned: one dword store)
             continue;
         }
         for (int b = 0; b < 4; b++) {
             const int64_t i = i0 + b;
-            if (i >= 0 && i < len && p + b < A.cap) base[p + b] = HEAD ? zp_head_byte(q, size, i) : src[i];
+            if (i >= 0 && i < len && p + b < cap) base[p + b] = HEAD ? zp_head_byte(q, size, i) : src[i];
         }
     }
+}
+template <bool HEAD>
+BSDC_HD void zp_copy(const ZpArgs &A, const ZpRec &q, uint32_t size, const uint8_t *buf, int64_t buf_n, const uint8_t *src,
+                   int64_t len, int64_t o, int lane, int nlanes) {
+    zp_copy_to<HEAD>(A.dst, A.cap, q, size, buf, buf_n, src, len, o, lane, nlanes);
 }
 
 // what rule 5 does to a partner's tag of an output record with flag 0x10: 0 nothing, 1 reversed, 2 reverse-complemented
@@ -322,6 +332,74 @@ int32_t zs_check(const char *who, const uint64_t *keys, const uint32_t *idx, int
     return 0;
 }
 
+// ---- the gather (cli zipper --stream's merge rounds) ----
+
+struct ZgArgs {
+    const uint32_t *order;
+    const int64_t *src_off;
+    const int32_t *src_len;
+    const uint8_t *src;
+    int64_t src_bytes;
+    int64_t n_fam;  // the records (the scan's name for its items)
+    int64_t *off;
+    uint8_t *dst;
+    int64_t cap;
+    int64_t *bsum;  // [groups + 1]
+    int64_t groups;
+};
+
+// output record k: its source bytes; an order entry >= n or an entry that leaves src is a record of no bytes
+BSDC_HD int64_t zg_rec(const ZgArgs &A, int64_t k, const uint8_t **from) {
+    const uint32_t s = A.order[k];
+    if ((int64_t)s >= A.n_fam) return 0;
+    const int64_t o = A.src_off[s], n = A.src_len[s];
+    if (n <= 0 || n > kZipMaxRec || o < 0 || o + n > A.src_bytes) return 0;
+    *from = A.src + o;
+    return n;
+}
+BSDC_HD int64_t scan_bytes(const ZgArgs &A, int64_t k, int) {
+    const uint8_t *from;
+    return zg_rec(A, k, &from);
+}
+BSDC_HD int64_t *scan_off(const ZgArgs &A, int) { return A.off; }
+
+BSDC_HD void zg_copy(const ZgArgs &A, int64_t k, int64_t o, int lane, int nlanes) {
+    const uint8_t *from = A.src;
+    const int64_t n = zg_rec(A, k, &from);
+    if (n) zp_copy_to<false>(A.dst, A.cap, ZpRec(), 0, A.src, A.src_bytes, from, n, o, lane, nlanes);
+}
+
+// the arguments, as the launcher and the twin both refuse them (host copies of order, src_off, src_len); fills A
+int32_t zg_check(const char *who, const uint32_t *order, const uint32_t *order_host, int64_t n, const int64_t *src_off,
+                 const int64_t *src_off_host, const int32_t *src_len, const int32_t *src_len_host, const uint8_t *src,
+                 int64_t src_bytes, int64_t *off, uint8_t *dst, int64_t cap, ZgArgs *A) {
+    const std::string w(who);
+    if (n < 0 || n > (int64_t)1 << 30) return zp_fail(w + ": n is negative or beyond 2^30");
+    if (src_bytes < 0 || cap < 0) return zp_fail(w + ": a negative byte count");
+    if (!order || !order_host) return zp_fail(w + ": order is null");
+    if (!src_off || !src_off_host || !src_len || !src_len_host) return zp_fail(w + ": src_off or src_len is null");
+    if (!src) return zp_fail(w + ": src is null");
+    if (!off) return zp_fail(w + ": off is null");
+    if (!dst) return zp_fail(w + ": dst is null");
+    if (((uintptr_t)src & 3u) || ((uintptr_t)dst & 3u) || ((uintptr_t)order & 3u) || ((uintptr_t)src_len & 3u))
+        return zp_fail(w + ": src, dst, order and src_len must be 4-byte aligned");
+    if (((uintptr_t)off & 7u) || ((uintptr_t)src_off & 7u)) return zp_fail(w + ": off and src_off must be 8-byte aligned");
+    for (int64_t k = 0; k < n; k++) {
+        const int64_t o = src_off_host[k], len = src_len_host[k];
+        if (len < 0 || len > kZipMaxRec || o < 0 || o + len > src_bytes)
+            return zp_fail(w + ": record " + std::to_string(k) + ": its bytes leave src");
+    }
+    int64_t need = 0;
+    for (int64_t k = 0; k < n; k++) {
+        if ((int64_t)order_host[k] >= n) return zp_fail(w + ": order[" + std::to_string(k) + "] is not below n");
+        need += src_len_host[order_host[k]];
+    }
+    if (cap < need) return zp_fail(w + ": cap " + std::to_string(cap) + " is below the records' bytes " + std::to_string(need));
+    A->order = order, A->src_off = src_off, A->src_len = src_len, A->src = src, A->src_bytes = src_bytes;
+    A->n_fam = n, A->off = off, A->dst = dst, A->cap = cap, A->bsum = nullptr, A->groups = 0;
+    return 0;
+}
+
 #ifdef __HIPCC__
 struct ZsArgs {
     const uint64_t *kin;
@@ -410,6 +488,13 @@ __global__ __launch_bounds__(kT) void k_zip_write(ZpArgs A) {
     zp_emit<true>(A, q, A.stat[k * kZipStat], A.off[k], threadIdx.x & 63, 64);
 }
 
+// one wavefront per output record, as k_zip_write: a lane owns one aligned destination dword at a time
+__global__ __launch_bounds__(kT) void k_zip_gather(ZgArgs A) {
+    const int64_t k = (int64_t)blockIdx.x * (kT / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (k >= A.n_fam) return;
+    zg_copy(A, k, A.off[k], threadIdx.x & 63, 64);
+}
+
 int64_t zs_tiles(int64_t n) { return (n + kZsTile - 1) / kZsTile; }
 int64_t zs_groups(int64_t n) { return (zs_tiles(n) * kZsBins + kFamPerGroup - 1) / kFamPerGroup; }
 int64_t zp_groups(int64_t n) { return (n + kFamPerGroup - 1) / kFamPerGroup; }
@@ -448,6 +533,48 @@ int64_t bsdc_zip_scan_host(const uint8_t *bytes, int64_t n_bytes, bsdc_zip_src *
         p += 4 + bs;
     }
     return n;
+}
+
+int64_t bsdc_zip_scan_prefix_host(const uint8_t *bytes, int64_t n_bytes, bsdc_zip_src *out, int64_t cap, int64_t *consumed) {
+    if (!bytes || n_bytes < 0 || cap < 0 || !consumed) return zp_fail("bsdc_zip_scan_prefix_host: a null or negative argument");
+    int64_t n = 0, p = 0;
+    for (; p + 36 <= n_bytes; n++) {
+        const std::string at = "bsdc_zip_scan_prefix_host: record " + std::to_string(n);
+        const uint8_t *r = bytes + p;
+        int32_t f[9];
+        memcpy(f, r, 36);
+        const int64_t bs = f[0];
+        const int l_name = r[12], n_cig = (int)((uint32_t)f[4] & 0xffffu);
+        const int64_t l_seq = f[5];
+        const int64_t body = 36 + (int64_t)l_name + 4 * (int64_t)n_cig + (l_seq + 1) / 2 + l_seq;
+        // (the fixed fields are all there: lengths that leave the record are an error, cut or not)
+        if (bs < 32 || l_seq < 0 || l_name < 2 || body > 4 + bs || 4 + bs > kZipMaxRec) return zp_fail(at + ": malformed lengths");
+        if (p + 4 + bs > n_bytes) break;  // the cut record: the caller's carry
+        if (out && n < cap) {
+            bsdc_zip_src &e = out[n];
+            e.off = p, e.len = (int32_t)(4 + bs), e.aux = (int32_t)body, e.ref_id = f[1], e.pos = f[2];
+            e.flag = (uint16_t)((uint32_t)f[4] >> 16), e.name_len = (uint8_t)(l_name - 1), e.reserved0 = 0, e.reserved = 0;
+        }
+        p += 4 + bs;
+    }
+    *consumed = p;
+    return n;
+}
+
+int32_t bsdc_zip_gather_host(const uint32_t *order, int64_t n, const int64_t *src_off, const int32_t *src_len, const uint8_t *src,
+                             int64_t src_bytes, int64_t *off, uint8_t *dst, int64_t cap) {
+    ZgArgs A;
+    if (const int32_t rc = zg_check("bsdc_zip_gather_host", order, order, n, src_off, src_off, src_len, src_len, src, src_bytes,
+                                    off, dst, cap, &A))
+        return rc;
+    int64_t o = 0;
+    for (int64_t k = 0; k < n; k++) {
+        off[k] = o;
+        zg_copy(A, k, o, 0, 1);
+        o += scan_bytes(A, k, 0);
+    }
+    off[n] = o;
+    return 0;
 }
 
 int32_t bsdc_zip_sort_host(uint64_t *keys, uint32_t *idx, int64_t n, int32_t max_ref, int32_t max_pos) {
@@ -560,6 +687,32 @@ int32_t bsdc_zip_format(const uint32_t *idx, int64_t n, const bsdc_zip_rec *tab,
     if (wgs) hipLaunchKernelGGL(k_zip_write, dim3(wgs), dim3(kT), 0, st, A);
     if (hipGetLastError() != hipSuccess) {
         g_zp_err = "bsdc_zip_format: a kernel launch failed";
+        return BSDC_EDEVICE;
+    }
+    return 0;
+}
+
+int64_t bsdc_zip_gather_tmp_bytes(int64_t n) {
+    if (n < 0) return -1;
+    return (zp_groups(n) + 1) * (int64_t)sizeof(int64_t) + 8;
+}
+
+int32_t bsdc_zip_gather(const uint32_t *order, const uint32_t *order_host, int64_t n, const int64_t *src_off,
+                        const int64_t *src_off_host, const int32_t *src_len, const int32_t *src_len_host, const uint8_t *src,
+                        int64_t src_bytes, int64_t *off, uint8_t *dst, int64_t cap, uint8_t *tmp, void *stream) {
+    ZgArgs A;
+    if (const int32_t rc = zg_check("bsdc_zip_gather", order, order_host, n, src_off, src_off_host, src_len, src_len_host, src,
+                                    src_bytes, off, dst, cap, &A))
+        return rc;
+    if (!tmp || ((uintptr_t)tmp & 7u)) return zp_fail("bsdc_zip_gather: tmp is null or not 8-byte aligned");
+    A.groups = zp_groups(n);
+    A.bsum = reinterpret_cast<int64_t *>(tmp);
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned wgs = (unsigned)((n + kT / 64 - 1) / (kT / 64));
+    launch_scan<1>(A, st);
+    if (wgs) hipLaunchKernelGGL(k_zip_gather, dim3(wgs), dim3(kT), 0, st, A);
+    if (hipGetLastError() != hipSuccess) {
+        g_zp_err = "bsdc_zip_gather: a kernel launch failed";
         return BSDC_EDEVICE;
     }
     return 0;

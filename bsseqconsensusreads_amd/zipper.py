@@ -13,6 +13,7 @@ the input of cli step5.  fgbio ZipperBams restated, parity unpinned.
 * ``zipper``  -- the driver: keys sorted (bsdc_zip_sort) and records written (bsdc_zip_format) on
   one GPU, then checksummed, deflated and packed there behind the BAM writer's sink.  host=True
   runs the host twins and the host deflate instead: for the tests, never chosen by cli.
+  stream=True: the same file with bounded memory (zipper_stream.py: sorted runs, merged on the GPU).
 """
 from __future__ import annotations
 
@@ -34,6 +35,15 @@ CONSENSUS_REVERSE = ("ad", "ae", "bd", "be", "cd", "ce", "aq", "bq")  # the word
 CONSENSUS_REVCOMP = ("ac", "bc")                                      # ... and in --tags-to-revcomp
 
 
+def _block_raw(path: str, block: bytes, at: int) -> bytes:
+    """One whole BGZF block (which starts at byte `at` of the file) inflated, its CRC32 and ISIZE checked."""
+    raw = zlib.decompress(block[18:-8], -15)
+    crc, isize = struct.unpack_from("<II", block, len(block) - 8)
+    if len(raw) != isize or zlib.crc32(raw) != crc:
+        raise OSError("%s: corrupt BGZF block at byte %d" % (path, at))
+    return raw
+
+
 def _inflate(path: str, threads: int = 0) -> bytes:
     """A BGZF file's uncompressed bytes (every block's CRC32 and ISIZE checked)."""
     data = open(path, "rb").read()
@@ -49,11 +59,7 @@ def _inflate(path: str, threads: int = 0) -> bytes:
 
     def one(c):
         a, n = c
-        raw = zlib.decompress(data[a + 18:a + n - 8], -15)
-        crc, isize = struct.unpack_from("<II", data, a + n - 8)
-        if len(raw) != isize or zlib.crc32(raw) != crc:
-            raise OSError("%s: corrupt BGZF block at byte %d" % (path, a))
-        return raw
+        return _block_raw(path, data[a:a + n], a)
     if threads > 1 and len(cuts) > 1:
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(int(threads)) as ex:
@@ -99,8 +105,22 @@ def scan(buf: np.ndarray, n_bytes: int) -> np.ndarray:
     return src
 
 
-def read_records(path: str, threads: int = 0) -> Records:
-    data = _inflate(path, threads)
+def scan_prefix(buf: np.ndarray, n_bytes: int):
+    """The whole records at the front of buf[:n_bytes] listed (bsdc_zip_scan_prefix_host) -> (their
+    list, the bytes they take): a record cut by the end is left to the caller's next piece."""
+    lib = _lib.load()
+    used = C.c_int64(0)
+    n = int(lib.bsdc_zip_scan_prefix_host(buf.ctypes.data, int(n_bytes), None, 0, C.byref(used)))
+    if n < 0:
+        raise ValueError(lib.bsdc_zip_last_error().decode())
+    src = np.zeros(n, _lib.ZIP_SRC)
+    if n and lib.bsdc_zip_scan_prefix_host(buf.ctypes.data, int(n_bytes), src.ctypes.data, n, C.byref(used)) != n:
+        raise ValueError(lib.bsdc_zip_last_error().decode())
+    return src, int(used.value)
+
+
+def parse_header(path: str, data: bytes):
+    """The BAM header at the front of the inflated bytes -> (BamHeader, the first record's byte)"""
     if data[:4] != b"BAM\1" or len(data) < 12:
         raise OSError("%s: not a BAM" % path)
     lt = struct.unpack_from("<i", data, 4)[0]
@@ -114,13 +134,19 @@ def read_records(path: str, threads: int = 0) -> Records:
         names.append(data[o + 4:o + 4 + ln - 1].decode())
         lens.append(struct.unpack_from("<i", data, o + 4 + ln)[0])
         o += 8 + ln
+    return bam.BamHeader(text, names, np.asarray(lens, np.int64)), o
+
+
+def read_records(path: str, threads: int = 0) -> Records:
+    data = _inflate(path, threads)
+    hdr, o = parse_header(path, data)
     buf = _aligned_copy(data[o:])
     n_bytes = len(data) - o
     try:
         src = scan(buf, n_bytes)
     except ValueError as e:
         raise OSError("%s: %s" % (path, e)) from None
-    return Records(bam.BamHeader(text, names, np.asarray(lens, np.int64)), buf, n_bytes, src)
+    return Records(hdr, buf, n_bytes, src)
 
 
 def tag_list(names: Optional[Sequence[str]], consensus: Tuple[str, ...]) -> Tuple[bytes, ...]:
@@ -211,7 +237,15 @@ def sort_keys(ref_id, pos, flag) -> np.ndarray:
 def tables(a: Records, u: Records, partner: np.ndarray) -> Tables:
     """Rules 2 and 6's inputs: the records of ALIGNED without flag 0x4, each with its partner's aux."""
     keep = np.nonzero((a.src["flag"] & 4) == 0)[0]
-    s, p = a.src[keep], u.src[np.asarray(partner, np.int64)[keep]]
+    p = u.src[np.asarray(partner, np.int64)[keep]]
+    pl = (p["len"] - p["aux"]).astype(np.int64)
+    return kept_tables(a, keep, pl, p["flag"], u.buf[_ragged(p["off"] + p["aux"], pl)])
+
+
+def kept_tables(a: Records, keep: np.ndarray, pl: np.ndarray, pflag: np.ndarray, part: np.ndarray) -> Tables:
+    """tables() of the kept records a.src[keep], given their partners' aux lengths, flags and aux
+    bytes back to back (what a chunk of --stream true holds of UNMAPPED)."""
+    s = a.src[keep]
     bad = np.nonzero((s["ref_id"] < 0) | (s["pos"] < -1))[0]
     if bad.shape[0]:
         raise ValueError("aligned read %r is mapped (no flag 0x4) but has no reference or position" % (
@@ -219,11 +253,9 @@ def tables(a: Records, u: Records, partner: np.ndarray) -> Tables:
     n = int(keep.shape[0])
     tab = np.zeros(n, _lib.ZIP_REC)
     tab["rec_off"], tab["rec_len"], tab["aux_start"] = s["off"], s["len"], s["aux"]
-    pl = (p["len"] - p["aux"]).astype(np.int64)
     tab["part_len"] = pl
     tab["part_off"] = np.cumsum(pl) - pl
-    tab["flag_or"] = p["flag"] & 0x200
-    part = u.buf[_ragged(p["off"] + p["aux"], pl)]
+    tab["flag_or"] = pflag & 0x200
     part = np.concatenate([part, np.zeros((-int(part.shape[0])) % 4 or (4 if part.shape[0] == 0 else 0), np.uint8)])
     return Tables(tab, part, sort_keys(s["ref_id"], s["pos"], s["flag"]), np.arange(n, dtype=np.uint32),
                   int(s["ref_id"].max()) if n else 0, int(s["pos"].max()) if n else 0)
@@ -318,10 +350,15 @@ def format_device(device, t: Tables, rec: np.ndarray, tags):
 
 def zipper(aligned: str, unmapped: str, out: str, tags_to_reverse: Sequence[str] = (), tags_to_revcomp: Sequence[str] = (),
            tags_to_remove: Sequence[str] = (), threads: int = 0, level: int = 6, device=0, info: Optional[str] = None,
-           host: bool = False) -> dict:
+           host: bool = False, stream: bool = False, chunk_bytes: Optional[int] = None, tmp_dir: Optional[str] = None) -> dict:
     """ALIGNED.bam + UNMAPPED.bam -> OUT.bam (module docstring; rules in DESIGN.md 3.11).  Both
-    inputs are read whole.  -> the info dict (also written to `info` as JSON)."""
+    inputs are read whole, unless `stream`: then memory is bounded by chunk_bytes (sorted runs under
+    tmp_dir, merged on the GPU: zipper_stream.py).  -> the info dict (also written to `info` as JSON)."""
     from . import bgzf
+    if stream:
+        from . import zipper_stream
+        return zipper_stream.zipper_stream(aligned, unmapped, out, tags_to_reverse, tags_to_revcomp, tags_to_remove, threads,
+                                           level, device, info, host, chunk_bytes, tmp_dir)
     a, u = read_records(aligned, threads), read_records(unmapped, threads)
     tags = tags_struct(tag_list(tags_to_reverse, CONSENSUS_REVERSE), tag_list(tags_to_revcomp, CONSENSUS_REVCOMP),
                        tag_list(tags_to_remove, ()))

@@ -568,7 +568,27 @@ const char *bsdc_toolrec_last_error(void);
  *
  * bsdc_zip_scan_host: the records of `bytes` (BAM records back to back, as they lie behind the
  * header) listed into out [cap] -> their count (call with out NULL to count), < 0 on a record that
- * is truncated or whose lengths leave it. */
+ * is truncated or whose lengths leave it.
+ *
+ * (new exports, ABI 19 still) cli zipper --stream true (DESIGN.md 3.11 "Streaming", 8.12):
+ *
+ * bsdc_zip_scan_prefix_host: bsdc_zip_scan_host for a piece of a file: the whole records at the
+ * front of `bytes` are listed and *consumed receives their bytes; a record cut by the end of the
+ * piece ends the list and is no error.  A record whose fixed fields are there and whose lengths
+ * leave it is an error (< 0), cut or not.
+ *
+ * bsdc_zip_gather: output record k is source record order[k]: off [n + 1] receives the exclusive
+ * prefix sum of src_len[order[k]] (the offset scan bsdc_zip_format uses) and dst + off[k] the bytes
+ * src + src_off[order[k]] .. + src_len[order[k]], unchanged.  One wavefront per record; dst is
+ * written in aligned dwords, each built from aligned source dwords by a funnel shift, heads and
+ * tails byte-wise, at any alignment of the records on both sides.  No byte at or past dst + cap is
+ * written; no byte outside src .. src + src_bytes is read.  order, src_off, src_len, src, off, dst,
+ * tmp (bsdc_zip_gather_tmp_bytes(n), 8-byte aligned): device pointers, src and dst 4-byte aligned;
+ * order_host, src_off_host, src_len_host: the caller's host copies, which are what gets checked.
+ * BSDC_EINVAL before anything is enqueued, with the reason in bsdc_zip_last_error: a NULL pointer,
+ * a negative count, an entry that leaves src, an order entry >= n, a cap below the sum of the
+ * lengths.  bsdc_zip_gather_host: the same on host pointers (no host copies: it checks what it
+ * reads). */
 #define BSDC_ZIP_MAX_TAGS 32
 typedef struct {
     int64_t rec_off;   /* the aligned record (its block_size field) in rec */
@@ -609,6 +629,13 @@ int32_t bsdc_zip_format_host(const uint32_t *idx, int64_t n, const bsdc_zip_rec 
                              const uint8_t *part, int64_t part_bytes, const bsdc_zip_tags *tags, int64_t *off, uint8_t *dst,
                              int64_t cap);
 int64_t bsdc_zip_scan_host(const uint8_t *bytes, int64_t n_bytes, bsdc_zip_src *out, int64_t cap);
+int64_t bsdc_zip_scan_prefix_host(const uint8_t *bytes, int64_t n_bytes, bsdc_zip_src *out, int64_t cap, int64_t *consumed);
+int64_t bsdc_zip_gather_tmp_bytes(int64_t n);
+int32_t bsdc_zip_gather(const uint32_t *order, const uint32_t *order_host, int64_t n, const int64_t *src_off,
+                        const int64_t *src_off_host, const int32_t *src_len, const int32_t *src_len_host, const uint8_t *src,
+                        int64_t src_bytes, int64_t *off, uint8_t *dst, int64_t cap, uint8_t *tmp, void *stream);
+int32_t bsdc_zip_gather_host(const uint32_t *order, int64_t n, const int64_t *src_off, const int32_t *src_len, const uint8_t *src,
+                             int64_t src_bytes, int64_t *off, uint8_t *dst, int64_t cap);
 const char *bsdc_zip_last_error(void);
 
 /* (new exports, ABI 19 still) cli group: paired-UMI molecule ids for the templates of a tagged BAM
